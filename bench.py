@@ -1,8 +1,28 @@
 #!/usr/bin/env python3
 """bench.py -- stencil_smi Jacobi GCell/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--fake-host]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--fake-host] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and nothing else: it sets
+up, warms up, times the K steps and prints the result line (metric, value,
+unit, ms_per_step, the configuration).  --full adds everything else described
+below to the same line: the profiled repetition and its roofline, the
+repetition statistics, the parity check against the oracle, the CPU baselines
+and the auxiliary measurements (--no-parity / --no-cpu-baseline / --no-aux
+drop single parts of a --full run).
+
+The warm-up's length depends on the clock, so after it the tile is put back
+to the seeded input (a device copy) and a fixed number of untimed runs of the
+timed plan follow (SETTLE_RUNS, each continuing on the buffers the last one
+left): the timed steps start from the same grid in every run, and the same
+arguments compute the same result in every run and every build.  --dump-outputs DIR
+writes what the timed steps returned -- the grid stencil.run hands its
+caller -- as float32 DIR/grid.npy (DIR/grid_rank<r>.npy with N > 1, every
+rank its own tile): the whole tile when the job's tiles fit 32 MiB together,
+else DIR/grid_sample.npy (grid_sample_rank<r>.npy), the cells at 32 MiB / N
+worth of sorted flat indices drawn by numpy's default_rng(2024 + rank) (the
+same indices in every run of the same tile size and N).
 
 With N > 1 and no WORLD_SIZE in the environment, bench.py launches its own
 ranks (the reference runs `mpirun -np 8 ./stencil_smi_host`, README.md:96):
@@ -31,7 +51,7 @@ region every kernel of that plan launches once and untimed runs of the same
 plan repeat for at least --warmup-ms (GPU clock settling; with N > 1 every rank
 runs the same number of them).
 
-The JSON line also carries:
+With --full the JSON line also carries:
   roofline      -- the stencil kernel with the largest measured time in the
                    timed region (HIP events on the launch stream: one marker
                    between back-to-back single-tile passes, so each launch is
@@ -96,6 +116,9 @@ AUX_BUDGET_S = 120.0           # watchdog on the auxiliary measurements
 WARMUP_MS = 50.0               # untimed warm-up floor (GPU clock settling)
 PARITY_MAX_STEPS = 64          # timed runs up to this many steps are re-run and checked whole
 PARITY_BOUNDED_STEPS = 48      # longer runs: the first 48 steps of the same pass structure
+SETTLE_RUNS = 3                # untimed runs of the timed plan between the input reset and the timed steps
+DUMP_BUDGET_BYTES = 32 << 20  # --dump-outputs: float32 bytes written by the whole job
+DUMP_SEED = 2024               # --dump-outputs: seed of the sampled cells of a tile over the budget
 
 
 def kernel_label(kind: int, tag: int) -> str:
@@ -617,6 +640,26 @@ def aux_collectives(comm, world: int, rank: int, stream, barrier) -> list:
     return out
 
 
+def dump_outputs(path: str, grid, rank: int, world: int) -> dict:
+    """--dump-outputs: write what the timed steps returned (`grid`, this
+    rank's tile as stencil.run handed it back) as float32 .npy under `path`:
+    the whole tile when the job's tiles fit DUMP_BUDGET_BYTES together, else
+    the cells at a fixed, seeded set of sorted flat indices (the same for
+    every run of this tile size and rank count)."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(grid.detach().cpu().numpy(), dtype=np.float32)
+    cells = max(1, DUMP_BUDGET_BYTES // 4 // world)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    if a.size <= cells:
+        name = f"grid{suffix}.npy"
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, a.size, cells))
+        a = a.reshape(-1)[idx]
+        name = f"grid_sample{suffix}.npy"
+    np.save(os.path.join(path, name), a)
+    return {"file": name, "shape": list(a.shape), "dtype": str(a.dtype), "of_cells": int(grid.numel())}
+
+
 def visible_gpus() -> int:
     """GPUs this process may use, counted without initialising HIP: the
     visibility variables when set, else the GPU nodes of the KFD topology."""
@@ -723,6 +766,11 @@ def main() -> None:
     ap.add_argument("--tile", type=int, default=TILE)
     ap.add_argument("--warmup-ms", type=float, default=WARMUP_MS,
                     help="untimed warm-up floor in ms (repeated runs of the timed plan) after the --warmup steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled repetition (roofline), the repetition "
+                         "statistics, the parity check, the CPU baselines and the auxiliary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the grid the timed steps returned (or a fixed seeded sample of it) as .npy under DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip re-running the timed plan from the seeded input and checking it against the oracle")
@@ -733,6 +781,8 @@ def main() -> None:
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="self-launch: kill every rank after this many seconds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
 
@@ -779,6 +829,9 @@ def main() -> None:
     X = Y = args.tile
     g = seeded_tile(rank, X, Y)
     tile = torch.from_numpy(g).cuda()
+    # the seeded input kept on the device: the warm-up steps the tile for a
+    # clock-dependent number of runs, the tile is put back to this copy after it
+    seeded = tile.clone()
     scratch = torch.empty_like(tile)
     # the highest priority, like the communicator's comm stream: a stream at
     # normal priority can share a hardware queue with RCCL's own streams, and
@@ -830,14 +883,92 @@ def main() -> None:
         warm_ms = (time.perf_counter() - t_w) * 1e3
         log(f"warm-up floor done ({warm_ms:.1f} ms)")
         # The timed region: exactly --steps steps, profiling off (no marker
-        # or event in it), bracketed by a barrier + device sync.
+        # or event in it), bracketed by a barrier + device sync.  The warm-up
+        # floor ran a clock-dependent number of runs, so the tile is put back
+        # to the seeded input first and SETTLE_RUNS untimed runs of the timed
+        # plan follow the copy: the timed steps start from the same grid in
+        # every run, and right behind their own kernels (20 steps timed
+        # straight after the copy kernel measured 7,450-8,340 GCell/s against
+        # 8,740-8,900 behind one to three runs of the plan and 8,670-8,790
+        # with no copy at all, alternating on one GPU).
+        tile.copy_(seeded)
+        for _ in range(SETTLE_RUNS):
+            stencil.run(comm, tile, args.steps, PX, PY, scratch)
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        stencil.run(comm, tile, args.steps, PX, PY, scratch)
+        res = stencil.run(comm, tile, args.steps, PX, PY, scratch)
         torch.cuda.synchronize()
         barrier()
         t1 = time.perf_counter()
+        # --dump-outputs: what the timed steps returned, kept on the device
+        # (a --full run steps the same buffers again below)
+        returned = res.clone() if args.dump_outputs and args.full else res
+    del seeded
+    elapsed = t1 - t0
+    if world > 1:  # the slowest rank's time
+        t = torch.tensor([elapsed], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0])
+    cells_per_gpu = X * Y
+    total_cells = cells_per_gpu * world
+    value = total_cells * args.steps / elapsed / 1e9
+    out = {
+        "metric": "Jacobi stencil GCell/s (8192^2 fp32 per GPU)",
+        "value": round(value, 2),
+        "unit": "GCell/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 6),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (uniform [0,1) fp32 grid, seed 1000+rank)",
+        "config": {
+            "workload": f"stencil_smi 4-point Jacobi, {X}x{Y} fp32 tile per GPU, "
+                        f"{PX}x{PY} decomposition ({PX * X}x{PY * Y} global)"
+                        + (", halo exchange over RCCL/xGMI overlapped with the interior" if world > 1
+                           else ", no halo exchange (BASELINE config 2)"),
+            "grid": [PX * X, PY * Y],
+            "tile": [X, Y],
+            "decomposition": [PX, PY],
+            "plan": [{"steps_per_pass": k, "passes": n} for k, n in plan["phases"]],
+            "tuning": stencil.get_tuning(),
+            "fusion": fusion,
+            "launch": "self (bench.py started the ranks)" if os.environ.get("SMI_BENCH_SELF_LAUNCH")
+                      else "external" if world > 1 else "single process",
+            "fake_host": bool(os.environ.get("SMI_BENCH_FAKE_HOST")),
+            "warmup_ms_floor": args.warmup_ms,
+            "warmup_ms_run": round(warm_ms, 1),
+            # the library's recorded source hash; load() refuses a library whose
+            # hash differs from this tree's (smi_amd.build._src_hash())
+            "lib_srchash": smi_amd._lib.recorded_srchash(),
+            "full": args.full,
+        },
+    }
+
+    printed = threading.Lock()
+
+    def emit(o):
+        if rank == 0 and printed.acquire(blocking=False):
+            data = (json.dumps(o) + "\n").encode()
+            while data:
+                data = data[os.write(result_fd, data):]
+
+    if not args.full:
+        # a plain run ends here: the outputs if asked for, and the line
+        log(f"timed region done: {args.steps} steps in {elapsed * 1e3:.3f} ms")
+        if args.dump_outputs:
+            out["outputs"] = dump_outputs(args.dump_outputs, returned, rank, world)
+        emit(out)
+        comm.finalize()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    with torch.cuda.stream(stream):
         # Per-kernel times: an identical repetition of the timed plan right
         # after it, with HIP events on each launch's stream (its wall time is
         # reported beside the timed one, never used for `value`).
@@ -870,7 +1001,6 @@ def main() -> None:
             torch.cuda.synchronize()
             barrier()
             rep_s.append(time.perf_counter() - ta)
-    elapsed = t1 - t0
     if world > 1:  # per repetition, the slowest rank's time
         t = torch.tensor(rep_s, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -914,9 +1044,6 @@ def main() -> None:
     sweeps = [k for k in kernels if k["kind"] != profiling.EDGE]
     dom = max(sweeps, key=lambda k: k["total_ms"]) if sweeps else None
 
-    cells_per_gpu = X * Y
-    total_cells = cells_per_gpu * world
-    value = total_cells * args.steps / elapsed / 1e9
     rep = np.array([total_cells * args.steps / t / 1e9 for t in rep_s])
     rep_mean = float(rep.mean())
     rep_sd = float(np.sqrt(((rep - rep_mean) ** 2).mean()))
@@ -945,39 +1072,7 @@ def main() -> None:
         # bands: the 1x1 pass's measured bytes scaled by the cells it stores
         traffic *= cells_launch / cells_per_gpu
         traffic_basis = "1x1 PMC pass scaled by the interior's cells per launch (estimate)"
-    out = {
-        "metric": "Jacobi stencil GCell/s (8192^2 fp32 per GPU)",
-        "value": round(value, 2),
-        "unit": "GCell/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (uniform [0,1) fp32 grid, seed 1000+rank)",
-        "config": {
-            "workload": f"stencil_smi 4-point Jacobi, {X}x{Y} fp32 tile per GPU, "
-                        f"{PX}x{PY} decomposition ({PX * X}x{PY * Y} global)"
-                        + (", halo exchange over RCCL/xGMI overlapped with the interior" if world > 1
-                           else ", no halo exchange (BASELINE config 2)"),
-            "grid": [PX * X, PY * Y],
-            "tile": [X, Y],
-            "decomposition": [PX, PY],
-            "plan": [{"steps_per_pass": k, "passes": n} for k, n in plan["phases"]],
-            "tuning": stencil.get_tuning(),
-            "fusion": fusion,
-            "launch": "self (bench.py started the ranks)" if os.environ.get("SMI_BENCH_SELF_LAUNCH")
-                      else "external" if world > 1 else "single process",
-            "fake_host": bool(os.environ.get("SMI_BENCH_FAKE_HOST")),
-            "warmup_ms_floor": args.warmup_ms,
-            "warmup_ms_run": round(warm_ms, 1),
-            # the library's recorded source hash; load() refuses a library whose
-            # hash differs from this tree's (smi_amd.build._src_hash())
-            "lib_srchash": smi_amd._lib.recorded_srchash(),
-        },
+    out.update({
         "repeats": repeats,
         "roofline": {
             "bound": "hbm",
@@ -1012,7 +1107,7 @@ def main() -> None:
                     "peak (what the memory system moved, over-fetch included). cell_step_GBs = 8 B per cell-STEP "
                     "x K steps per pass / launch time: temporal blocking, not a fraction of peak",
         },
-    }
+    })
     if dom:
         rp = (rocprof_avg(f"{'sweepd' if spl > 12 else 'sweepk'}_kernel<{spl}>")
               if dom["kind"] == profiling.SWEEPK else None)
@@ -1040,20 +1135,15 @@ def main() -> None:
             out["parity"] = verify_timed_plan(comm, tile, scratch, g, args.steps, PX, PY, rank, world)
         log(f"parity: {out['parity']['mismatches']} mismatching cells of {out['parity']['cells']} "
             f"({out['parity']['steps']} steps)")
+    if args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, returned, rank, world)
+        del returned
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
 
     # Auxiliary lines (BASELINE configs 4 and 5), measured after the timed
     # stencil region.  A watchdog bounds them: if they do not finish, rank 0
     # still prints the stencil line and every rank exits.
-    printed = threading.Lock()
-
-    def emit(o):
-        if rank == 0 and printed.acquire(blocking=False):
-            data = (json.dumps(o) + "\n").encode()
-            while data:
-                data = data[os.write(result_fd, data):]
-
     def watchdog():
         o = dict(out)
         o["aux"] = {"error": f"auxiliary measurements exceeded {AUX_BUDGET_S:.0f} s"}

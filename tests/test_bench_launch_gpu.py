@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_self_launch_two_ranks(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--fake-host", "--steps", "24",
-                        "--warmup", "2", "--no-aux", "--warmup-ms", "5", "--tile", "2048", "--launch-timeout", "150"],
+                        "--warmup", "2", "--full", "--no-aux", "--warmup-ms", "5", "--tile", "2048", "--launch-timeout", "150"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=200)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

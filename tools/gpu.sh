@@ -46,15 +46,15 @@ for st in "$@"; do
     rc=$?; grep -E "PASS|FAIL|ERROR|passed|failed" $O/hosts.log | tail -30; [ $rc -eq 0 ] || fail $st $rc
     ;;
   bench)
-    timeout -k 10 200 python bench.py $DRV > $O/bench_driver.json 2> $O/bench_driver.err || fail $st $?
+    timeout -k 10 200 python bench.py $DRV --full > $O/bench_driver.json 2> $O/bench_driver.err || fail $st $?
     summ $O/bench_driver.json
     ;;
   default)
-    timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err || fail $st $?
+    timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || fail $st $?
     summ $O/bench_default.json
     ;;
   prof)
-    (cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_driver -o run -- python3 $R/bench.py $DRV > $O/bench_prof_driver.json 2> $O/bench_prof_driver.err) || fail $st $?
+    (cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_driver -o run -- python3 $R/bench.py $DRV --full > $O/bench_prof_driver.json 2> $O/bench_prof_driver.err) || fail $st $?
     grep -h sweepd $O/prof_driver/*kernel_stats.csv | head -3
     ;;
   pmc)
@@ -87,7 +87,7 @@ for st in "$@"; do
     ;;
   fake)
     for n in ${FAKE_N:-2 4 8}; do
-      timeout -k 10 500 python bench.py --gpus $n --fake-host --steps 20 --warmup 5 --no-aux > $O/bench_fake$n.json 2> $O/bench_fake$n.err || fail fake$n $?
+      timeout -k 10 500 python bench.py --gpus $n --fake-host --steps 20 --warmup 5 --full --no-aux > $O/bench_fake$n.json 2> $O/bench_fake$n.err || fail fake$n $?
       python3 -c "import json;d=json.load(open('$O/bench_fake$n.json'));print('fake$n',d['value'],d['config']['decomposition'],d['parity']['bit_exact'],d['parity']['cells'])"
     done
     ;;
