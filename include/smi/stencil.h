@@ -46,6 +46,20 @@ int smi_stencil_step(const float *in, float *out, int x_local, int y_local,
                      const int mode[4], const float *const halo[4],
                      float *send_left, float *send_right, SMI_Stream stream);
 
+/* smi_stencil_step, and additionally max-accumulates the bit pattern of
+ * |out - in| over the cells this call writes into *resid_bits (device memory,
+ * 4-byte aligned; the caller zeroes it; calls may accumulate into one word).
+ * Each difference is one fp32 subtraction and fabs (subnormals kept); the
+ * patterns of non-negative floats order like the floats and every NaN pattern
+ * lies above +inf, so the word ends up holding max |out - in| exactly, or a
+ * NaN if any difference is one.  Cells of SMI_SIDE_SKIP sides are not written
+ * and do not contribute; copied (SMI_SIDE_COPY) cells contribute |c - c|.
+ * Same loads, arithmetic and stores as smi_stencil_step: no extra pass. */
+int smi_stencil_step_residual(const float *in, float *out, int x_local, int y_local,
+                              const int mode[4], const float *const halo[4],
+                              float *send_left, float *send_right,
+                              unsigned int *resid_bits, SMI_Stream stream);
+
 /* Full run of the stencil_smi program on this rank's tile: `timesteps`
  * Jacobi steps over the PX x PY decomposition of `comm` (PX*PY == size),
  * halos exchanged every step with the four neighbours through RCCL on a
@@ -65,6 +79,36 @@ int smi_stencil_step(const float *in, float *out, int x_local, int y_local,
 int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local,
                     int y_local, int px, int py, int timesteps,
                     SMI_Stream stream, int *result_index);
+
+/* Jacobi steps until the residual of a checked step is <= tol, or max_steps.
+ * The residual of step t is r_t = max over the global grid of
+ * |x_t - x_{t-1}| (the contract of smi_stencil_step_residual: exact, no
+ * summation order; NaN if any difference is NaN).  Check points are
+ * t_j = min(j * check_every, max_steps), j = 1, 2, ...: the steps between two
+ * check points run as smi_stencil_run runs that many steps (same plan under
+ * the current fusion setting), step t_j itself is one single step with the
+ * residual fused into its kernels.  The local bit pattern then goes through
+ * an integer-max smi_reduce to rank 0 and an smi_bcast, so every rank sees
+ * the same r_t and stops at the same step: the first check point with
+ * r_t <= tol (a NaN never satisfies it), or max_steps -- which still returns
+ * SMI_SUCCESS, with *converged = 0.
+ *   *steps_done   steps taken
+ *   *residual     the last r_t checked (+inf if max_steps == 0)
+ *   *converged    (nullable) residual <= tol
+ *   *result_index the buffer holding x_{steps_done}; it is bit-identical to
+ *                 smi_stencil_run(timesteps = steps_done) from the same start
+ * tol >= 0 and not NaN, max_steps >= 0, check_every >= 1; tile rules as for
+ * smi_stencil_run.  Collective: every rank of `comm` calls it with the same
+ * tol, max_steps and check_every; it issues bulk operations on `comm`.
+ * SYNCHRONOUS with the host at every check point: 4 bytes are copied back
+ * and `stream` is synchronised there, so a check costs one single step (8
+ * B/cell where the fused passes move 8 B/cell per up to 20 steps), the
+ * reduce + bcast and a host round trip; choose check_every so that this is
+ * small beside the steps in between. */
+int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local,
+                      int px, int py, float tol, int max_steps, int check_every,
+                      SMI_Stream stream, int *result_index, int *steps_done,
+                      float *residual, int *converged);
 
 /* Tuning knobs of the sweep kernel (row-block height, rows in flight per
  * wave, non-temporal stores, 1 = overlap halo exchange with the interior).

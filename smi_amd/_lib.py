@@ -59,7 +59,10 @@ SIGNATURES = {
     "smi_device_count": (I, [ctypes.POINTER(I)]),
     "smi_stream_synchronize": (I, [P]),
     "smi_stencil_step": (I, [P, P, I, I, ctypes.POINTER(I), ctypes.POINTER(P), P, P, P]),
+    "smi_stencil_step_residual": (I, [P, P, I, I, ctypes.POINTER(I), ctypes.POINTER(P), P, P, P, P]),
     "smi_stencil_run": (I, [SMI_Comm, P, P, I, I, I, I, I, P, ctypes.POINTER(I)]),
+    "smi_stencil_solve": (I, [SMI_Comm, P, P, I, I, I, I, F, I, I, P, ctypes.POINTER(I), ctypes.POINTER(I),
+                              ctypes.POINTER(F), ctypes.POINTER(I)]),
     "smi_stencil_set_tuning": (I, [I, I, I, I]),
     "smi_stencil_get_tuning": (I, [ctypes.POINTER(I)] * 4),
     "smi_stencil_set_fusion": (I, [I, I, I]),

@@ -290,6 +290,8 @@ int smi_finalize(SMI_Comm comm) {
     for (auto e : c->events) SMI_HIP_CHECK(hipEventDestroy(e));
     if (c->work) SMI_HIP_CHECK(hipFree(c->work));
     if (c->halo) SMI_HIP_CHECK(hipFree(c->halo));
+    if (c->resid) SMI_HIP_CHECK(hipFree(c->resid));
+    if (c->resid_host) SMI_HIP_CHECK(hipHostFree(c->resid_host));
     if (c->comm_stream) SMI_HIP_CHECK(hipStreamDestroy(c->comm_stream));
     if (c->interior_stream) SMI_HIP_CHECK(hipStreamDestroy(c->interior_stream));
     return drain_rc;

@@ -125,6 +125,11 @@ struct Comm {
     // halo staging for the stencil: [top, bottom, left, right] in + send L/R
     float *halo = nullptr;
     size_t halo_elems = 0;
+    // smi_stencil_solve: two device words (this rank's residual bits, the
+    // reduced bits) and the pinned host word they are read back into; made by
+    // the first solve, freed with the communicator
+    unsigned int *resid = nullptr;
+    unsigned int *resid_host = nullptr;
     std::vector<hipEvent_t> events;  // reusable sync events
     std::shared_ptr<void> chan_engine;  // element-granular channels (channels.cpp)
 };

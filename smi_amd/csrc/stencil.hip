@@ -18,8 +18,45 @@
 #include <algorithm>
 
 #include "stencil_common.h"
+#include "stencil_resid.h"
 
 namespace smi {
+
+// Bit pattern of |o - c|: one IEEE fp32 subtraction (subnormals kept), the
+// sign bit cleared.  inf - inf and any NaN operand give a NaN pattern.
+__device__ __forceinline__ unsigned int absdiff_bits(float o, float c) {
+    return __builtin_bit_cast(unsigned int, __fsub_rn(o, c)) & 0x7fffffffu;
+}
+
+// Unsigned max over the 64 lanes of a wave, left in lane 63 (DPP; a lane
+// without a source keeps the identity 0).  row_shr 1, 2, 4, 8 leave each
+// row's max in its lane 15; row_bcast:15 folds rows 0 -> 1 and 2 -> 3,
+// row_bcast:31 folds lane 31 into rows 2 and 3.  Call with all lanes active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned int dpp_or0(unsigned int x) {
+    return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ unsigned int wave_max_u32(unsigned int v) {
+    v = max(v, dpp_or0<0x111, 0xf>(v));
+    v = max(v, dpp_or0<0x112, 0xf>(v));
+    v = max(v, dpp_or0<0x114, 0xf>(v));
+    v = max(v, dpp_or0<0x118, 0xf>(v));
+    v = max(v, dpp_or0<0x142, 0xa>(v));
+    v = max(v, dpp_or0<0x143, 0xc>(v));
+    return v;
+}
+
+// A wave's maximum into the residual word (one lane calls this).  The word
+// only grows, so a wave that cannot raise it sends no atomic: every atomic on
+// the one address is a serial round trip to the memory side (~8 ns each; an
+// 8192^2 step has ~22 k waves, and posting all of them took 0.265 ms against
+// the plain step's 0.090, profiles/solve/).  The reading is a device-scope
+// load; one that is stale can only be too low and costs an atomic that
+// changes nothing.
+__device__ __forceinline__ void resid_post(unsigned int *resid, unsigned int m) {
+    if (m == 0) return;
+    if (m > __hip_atomic_load(resid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(resid, m);
+}
 
 // One wave = one strip of 256 columns x `ht` rows; 4 waves per block take 4
 // consecutive (row-block, strip) tasks, strip fastest.  U rows are fetched
@@ -27,10 +64,18 @@ namespace smi {
 // All control values are wave-uniform (readfirstlane) and every load is
 // unconditional with a clamped address, so the loop body has no divergent
 // control flow around its loads and the compiler emits counted vmcnt waits.
-template <int U, bool NT>
-__global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ in,
-                                                    float *__restrict__ out, SweepArgs a,
-                                                    int nstrips, int nrb, int ht) {
+//
+// RES: the residual variant (smi_stencil_step_residual).  Same loads,
+// arithmetic and stores; every lane also keeps the largest bit pattern of
+// |o - c| over the cells it stores (c is the centre value already in
+// registers), the wave folds the 64 lanes with DPP and its last lane issues at most
+// one atomic max on *resid.  Patterns of non-negative floats order like the
+// floats and every NaN pattern lies above +inf, so an unsigned max is the
+// exact max-norm and carries a NaN without a branch.
+template <int U, bool NT, bool RES>
+__device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *__restrict__ out,
+                                           const SweepArgs &a, int nstrips, int nrb, int ht,
+                                           unsigned int *resid) {
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
     const int lane = threadIdx.x & 63;
     const int task = __builtin_amdgcn_readfirstlane(lb * 4 + (int)(threadIdx.x >> 6));
@@ -74,6 +119,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ in
     auto ldw = [&](int r) -> float { return wbase[(size_t)r * wstride]; };
     auto lde = [&](int r) -> float { return ebase[(size_t)r * estride]; };
 
+    unsigned int rmax = 0;  // RES: this lane's largest |o - c| pattern
     auto do_row = [&](int r, float4 n, float4 c, float4 s, float ew, float ee) {
         const bool row_skip = (r == 0 && mT == SMI_SIDE_SKIP) || (r == rows - 1 && mB == SMI_SIDE_SKIP);
         const bool row_copy = (r == 0 && mT == SMI_SIDE_COPY) || (r == rows - 1 && mB == SMI_SIDE_COPY);
@@ -91,6 +137,14 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ in
         o.z = row_copy ? c.z : o.z;
         o.w = (copyR || row_copy) ? c.w : o.w;
         if (row_skip) return;  // wave-uniform
+        if constexpr (RES) {
+            // the cells stored below, and only those: a SKIP column's cell and
+            // the clamped lanes of a partial strip (copies of lane nl-1) stay out
+            const unsigned int dx = skipL ? 0u : absdiff_bits(o.x, c.x);
+            const unsigned int dw = skipR ? 0u : absdiff_bits(o.w, c.w);
+            const unsigned int d = max(max(dx, absdiff_bits(o.y, c.y)), max(absdiff_bits(o.z, c.z), dw));
+            rmax = max(rmax, act ? d : 0u);
+        }
         float *op = out + (size_t)r * cols + c0;
         if (plain_store) store4<NT>(op, o);
         if (part_store) {
@@ -144,13 +198,37 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ in
             }
         }
     }
+    if constexpr (RES) {
+        rmax = wave_max_u32(rmax);  // all 64 lanes are here: every exit above is wave-uniform
+        if (lane == 63) resid_post(resid, rmax);
+    }
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(256) void sweep_kernel(const float *__restrict__ in,
+                                                    float *__restrict__ out, SweepArgs a,
+                                                    int nstrips, int nrb, int ht) {
+    sweep_body<U, NT, false>(in, out, a, nstrips, nrb, ht, nullptr);
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(256) void sweep_res_kernel(const float *__restrict__ in,
+                                                        float *__restrict__ out, SweepArgs a,
+                                                        int nstrips, int nrb, int ht,
+                                                        unsigned int *__restrict__ resid) {
+    sweep_body<U, NT, true>(in, out, a, nstrips, nrb, ht, resid);
 }
 
 // Cells of the tile's halo-facing sides (those with side_mask bit set),
 // computed with the true side modes (COPY / HALO); also packs the new
 // first / last column for the left / right neighbours.  One thread per cell:
 // [0, cols) row 0, [cols, 2cols) row rows-1, then col 0, then col cols-1.
-__global__ __launch_bounds__(256) void edge_kernel(SweepArgs a, int side_mask) {
+// Returns the cell's |v - in| pattern for the residual variant (RES; costs the
+// one load of the centre value a computed cell does not otherwise need), 0
+// for a thread without a cell.  A corner cell is visited by two threads, which
+// a maximum does not notice.
+template <bool RES>
+__device__ __forceinline__ unsigned int edge_cell(const SweepArgs &a, int side_mask) {
     const int rows = a.rows, cols = a.cols;
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     int r, c, side;
@@ -158,8 +236,8 @@ __global__ __launch_bounds__(256) void edge_kernel(SweepArgs a, int side_mask) {
     else if ((t -= cols) < cols) { r = rows - 1; c = t; side = 1; }
     else if ((t -= cols) < rows) { r = t; c = 0; side = 2; }
     else if ((t -= rows) < rows) { r = t; c = cols - 1; side = 3; }
-    else return;
-    if (!(side_mask & (1 << side))) return;
+    else return 0;
+    if (!(side_mask & (1 << side))) return 0;
     const float *in = a.in;
     const size_t idx = (size_t)r * cols + c;
     const bool copy = (r == 0 && a.mode[0] == SMI_SIDE_COPY) ||
@@ -181,6 +259,18 @@ __global__ __launch_bounds__(256) void edge_kernel(SweepArgs a, int side_mask) {
     a.out[idx] = v;
     if (c == 0 && a.send_left) a.send_left[r] = v;
     if (c == cols - 1 && a.send_right) a.send_right[r] = v;
+    if constexpr (RES) return absdiff_bits(v, in[idx]);
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void edge_kernel(SweepArgs a, int side_mask) { edge_cell<false>(a, side_mask); }
+
+__global__ __launch_bounds__(256) void edge_res_kernel(SweepArgs a, int side_mask,
+                                                       unsigned int *__restrict__ resid) {
+    // every lane returns from edge_cell (with 0 if it has no cell) before the
+    // wave folds: one atomic max per wave
+    const unsigned int m = wave_max_u32(edge_cell<true>(a, side_mask));
+    if ((threadIdx.x & 63) == 63) resid_post(resid, m);
 }
 
 // Pack the first / last column of a tile (the initial halos that the
@@ -206,8 +296,14 @@ int check_tile(const float *in, const float *out, int rows, int cols) {
 
 template <int U>
 static void launch_sweep_u(const SweepArgs &a, int nstrips, int nrb, int ht, int blocks, bool nt,
-                           hipStream_t s) {
-    if (nt)
+                           unsigned int *resid, hipStream_t s) {
+    if (resid && nt)
+        hipLaunchKernelGGL((sweep_res_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
+                           nstrips, nrb, ht, resid);
+    else if (resid)
+        hipLaunchKernelGGL((sweep_res_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
+                           nstrips, nrb, ht, resid);
+    else if (nt)
         hipLaunchKernelGGL((sweep_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
                            nstrips, nrb, ht);
     else
@@ -215,7 +311,8 @@ static void launch_sweep_u(const SweepArgs &a, int nstrips, int nrb, int ht, int
                            nstrips, nrb, ht);
 }
 
-int launch_sweep(const SweepArgs &a, hipStream_t s) {
+// resid: nullptr = the plain kernels, else the residual variants
+int launch_sweep_res(const SweepArgs &a, unsigned int *resid, hipStream_t s) {
     const int ht = std::max(1, g_tune.ht);
     const int nstrips = (a.cols + 255) / 256;
     const int nrb = (a.rows + ht - 1) / ht;
@@ -224,27 +321,34 @@ int launch_sweep(const SweepArgs &a, hipStream_t s) {
     int tok = -1;
     if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_SWEEP, s, &tok, 1, (double)a.rows * a.cols));
     switch (g_tune.u) {
-    case 1: launch_sweep_u<1>(a, nstrips, nrb, ht, blocks, g_tune.nt, s); break;
-    case 2: launch_sweep_u<2>(a, nstrips, nrb, ht, blocks, g_tune.nt, s); break;
-    case 8: launch_sweep_u<8>(a, nstrips, nrb, ht, blocks, g_tune.nt, s); break;
-    case 16: launch_sweep_u<16>(a, nstrips, nrb, ht, blocks, g_tune.nt, s); break;
-    default: launch_sweep_u<4>(a, nstrips, nrb, ht, blocks, g_tune.nt, s); break;
+    case 1: launch_sweep_u<1>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
+    case 2: launch_sweep_u<2>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
+    case 8: launch_sweep_u<8>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
+    case 16: launch_sweep_u<16>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
+    default: launch_sweep_u<4>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
     }
     SMI_HIP_CHECK(hipGetLastError());
     if (tok >= 0) SMI_TRY(prof_end(tok, s));
     return SMI_SUCCESS;
 }
 
-int launch_edge(const SweepArgs &a, int side_mask, hipStream_t s) {
+int launch_sweep(const SweepArgs &a, hipStream_t s) { return launch_sweep_res(a, nullptr, s); }
+
+int launch_edge_res(const SweepArgs &a, int side_mask, unsigned int *resid, hipStream_t s) {
     const long cells = 2L * a.cols + 2L * a.rows;
     const int blocks = (int)((cells + 255) / 256);
     int tok = -1;
     if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_EDGE, s, &tok));
-    hipLaunchKernelGGL(edge_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask);
+    if (resid)
+        hipLaunchKernelGGL(edge_res_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask, resid);
+    else
+        hipLaunchKernelGGL(edge_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask);
     SMI_HIP_CHECK(hipGetLastError());
     if (tok >= 0) SMI_TRY(prof_end(tok, s));
     return SMI_SUCCESS;
 }
+
+int launch_edge(const SweepArgs &a, int side_mask, hipStream_t s) { return launch_edge_res(a, side_mask, nullptr, s); }
 
 int launch_pack_cols(const float *in, int rows, int cols, float *left, float *right, hipStream_t s) {
     hipLaunchKernelGGL(pack_cols_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, in, rows, cols, left, right);
@@ -279,12 +383,12 @@ int smi_stencil_get_tuning(int *rows_per_wave, int *rows_in_flight, int *nontemp
     return SMI_SUCCESS;
 }
 
-int smi_stencil_step(const float *in, float *out, int x_local, int y_local, const int mode[4],
-                     const float *const halo[4], float *send_left, float *send_right,
-                     SMI_Stream stream) {
+static int step_args(const float *in, float *out, int x_local, int y_local, const int mode[4],
+                     const float *const halo[4], float *send_left, float *send_right, SweepArgs *args) {
+    SweepArgs &a = *args;
     SMI_TRY(check_tile(in, out, x_local, y_local));
     SMI_ARG_CHECK(mode, "NULL mode array");
-    SweepArgs a{};
+    a = SweepArgs{};
     a.in = in;
     a.out = out;
     a.rows = x_local;
@@ -297,7 +401,24 @@ int smi_stencil_step(const float *in, float *out, int x_local, int y_local, cons
     }
     a.send_left = send_left;
     a.send_right = send_right;
+    return SMI_SUCCESS;
+}
+
+int smi_stencil_step(const float *in, float *out, int x_local, int y_local, const int mode[4],
+                     const float *const halo[4], float *send_left, float *send_right,
+                     SMI_Stream stream) {
+    SweepArgs a;
+    SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
     return launch_sweep(a, (hipStream_t)stream);
+}
+
+int smi_stencil_step_residual(const float *in, float *out, int x_local, int y_local, const int mode[4],
+                              const float *const halo[4], float *send_left, float *send_right,
+                              unsigned int *resid_bits, SMI_Stream stream) {
+    SweepArgs a;
+    SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
+    SMI_ARG_CHECK(resid_bits && ((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
+    return launch_sweep_res(a, resid_bits, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "stencil_common.h"
+#include "stencil_resid.h"
 
 namespace smi {
 
@@ -514,13 +515,11 @@ int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int tim
     return SMI_SUCCESS;
 }
 
-int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py,
-                    int timesteps, SMI_Stream stream_, int *result_index) {
-    Comm *c = lookup_comm(comm);
-    if (!c) {
-        set_error("unknown communicator");
-        return SMI_ERR_BAD_COMM;
-    }
+// smi_stencil_run (resid == nullptr), or -- for the checked step of
+// smi_stencil_solve -- the same schedule restricted to single steps whose
+// kernels also max-accumulate |out - in| into *resid (stencil.hip).
+static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local, int px, int py, int timesteps,
+                     SMI_Stream stream_, int *result_index, unsigned int *resid) {
     SMI_TRY(check_tile(buf0, buf1, x_local, y_local));
     SMI_ARG_CHECK(px >= 1 && py >= 1 && px * py == c->size, "px*py must equal the communicator size");
     SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
@@ -545,7 +544,14 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_
     for (int k = 0; k < 4; ++k)
         if (side_nb[k] >= 0) side_mask |= 1 << k;
 
-    const Plan plan = make_plan(rows, cols, timesteps, side_mask != 0);
+    Plan plan;
+    if (resid) {  // single steps only
+        plan.nph = timesteps > 0;
+        plan.k[0] = 1;
+        plan.n[0] = timesteps;
+    } else {
+        plan = make_plan(rows, cols, timesteps, side_mask != 0);
+    }
     *result_index = plan.passes() & 1;
     prof_break_chain();  // markers chain only between this run's own passes
     if (timesteps == 0) return SMI_SUCCESS;
@@ -607,7 +613,7 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_
                 } else {
                     a.in = bufp(cur);
                     a.out = bufp(cur ^ 1);
-                    SMI_TRY(launch_sweep(a, s));
+                    SMI_TRY(launch_sweep_res(a, resid, s));
                 }
             }
         }
@@ -796,13 +802,13 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_
                 a.in = inner.in = bufp(cur);
                 a.out = inner.out = bufp(cur ^ 1);
                 if (overlap) {
-                    SMI_TRY(pass([&](hipStream_t st, hipEvent_t) { return launch_edge(a, side_mask, st); },
-                                 [&](hipStream_t st, hipEvent_t) { return launch_sweep(inner, st); }, xchg1,
+                    SMI_TRY(pass([&](hipStream_t st, hipEvent_t) { return launch_edge_res(a, side_mask, resid, st); },
+                                 [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(inner, resid, st); }, xchg1,
                                  t < npass - 1, a.out, false));
                 } else {
                     // the full sweep reads the halos itself
                     SMI_TRY(pass([&](hipStream_t, hipEvent_t) { return (int)SMI_SUCCESS; },
-                                 [&](hipStream_t st, hipEvent_t) { return launch_sweep(a, st); }, xchg1,
+                                 [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(a, resid, st); }, xchg1,
                                  t < npass - 1, a.out, false));
                 }
             }
@@ -816,6 +822,67 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_
         SMI_HIP_CHECK(hipEventRecord(ev_fin, s));
         SMI_HIP_CHECK(hipStreamWaitEvent(user, ev_fin, 0));
     }
+    return SMI_SUCCESS;
+}
+
+int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py,
+                    int timesteps, SMI_Stream stream_, int *result_index) {
+    Comm *c = lookup_comm(comm);
+    if (!c) {
+        set_error("unknown communicator");
+        return SMI_ERR_BAD_COMM;
+    }
+    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, nullptr);
+}
+
+int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py, float tol,
+                      int max_steps, int check_every, SMI_Stream stream_, int *result_index, int *steps_done,
+                      float *residual, int *converged) {
+    // the scalar arguments first: no device, no communicator needed to refuse them
+    SMI_ARG_CHECK(tol >= 0.0f, "tol must be >= 0 and not NaN");  // false for a NaN
+    SMI_ARG_CHECK(max_steps >= 0, "max_steps < 0");
+    SMI_ARG_CHECK(check_every >= 1, "check_every must be >= 1");
+    SMI_ARG_CHECK(result_index && steps_done && residual, "NULL result_index, steps_done or residual");
+    Comm *c = lookup_comm(comm);
+    if (!c) {
+        set_error("unknown communicator");
+        return SMI_ERR_BAD_COMM;
+    }
+    SMI_TRY(check_tile(buf0, buf1, x_local, y_local));
+    SMI_ARG_CHECK(px >= 1 && py >= 1 && px * py == c->size, "px*py must equal the communicator size");
+    hipStream_t s = (hipStream_t)stream_;
+    if (!c->resid) SMI_HIP_CHECK(hipMalloc(&c->resid, 2 * sizeof(unsigned int)));
+    if (!c->resid_host) SMI_HIP_CHECK(hipHostMalloc(&c->resid_host, sizeof(unsigned int), hipHostMallocDefault));
+    unsigned int *local = c->resid, *global = c->resid + 1;
+
+    float *buf[2] = {buf0, buf1};
+    int cur = 0, done = 0, idx = 0;
+    float r = __builtin_inff();
+    while (done < max_steps) {
+        const int next = (int)std::min((long)done + check_every, (long)max_steps);
+        // the unchecked steps, exactly as smi_stencil_run plans that many
+        SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done - 1, stream_, &idx, nullptr));
+        cur ^= idx;
+        // the checked step; its kernels run on this communicator's streams,
+        // all ordered after `stream` here and joined back to it at the end
+        SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
+        SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, local));
+        cur ^= idx;
+        done = next;
+        // the same word on every rank: integer max of the patterns to rank 0
+        // and back (the float SMI_MAX starts from FLT_MIN, fold.h, and would
+        // turn a residual of 0 into 1.17549435e-38)
+        SMI_TRY(smi_reduce(comm, local, global, 1, SMI_INT, SMI_MAX, 0, 0, stream_));
+        SMI_TRY(smi_bcast(comm, global, 1, SMI_INT, 0, 0, stream_));
+        SMI_HIP_CHECK(hipMemcpyAsync(c->resid_host, global, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+        SMI_HIP_CHECK(hipStreamSynchronize(s));
+        r = __builtin_bit_cast(float, *c->resid_host);
+        if (r <= tol) break;  // never for a NaN
+    }
+    *result_index = cur;
+    *steps_done = done;
+    *residual = r;
+    if (converged) *converged = r <= tol;
     return SMI_SUCCESS;
 }
 

@@ -61,14 +61,47 @@ def _ptr(t: torch.Tensor | None) -> int | None:
 
 def step(inp: torch.Tensor, out: torch.Tensor, modes=(0, 0, 0, 0), halos=(None, None, None, None),
          send_left: torch.Tensor | None = None, send_right: torch.Tensor | None = None,
-         stream=None) -> None:
+         stream=None, residual: torch.Tensor | None = None) -> None:
     """One Jacobi step of one tile (smi_stencil_step).  modes per side
-    (top, bottom, left, right): SIDE_COPY / SIDE_HALO / SIDE_SKIP."""
+    (top, bottom, left, right): SIDE_COPY / SIDE_HALO / SIDE_SKIP.
+    residual: a one-element int32 device tensor (zeroed by the caller) that
+    the step max-accumulates the bit pattern of |out - inp| of the cells it
+    writes into (smi_stencil_step_residual; residual_value() decodes it)."""
     X, Y = inp.shape
     m = (ctypes.c_int * 4)(*modes)
     h = (ctypes.c_void_p * 4)(*[_ptr(t) for t in halos])
-    _lib.call("smi_stencil_step", inp.data_ptr(), out.data_ptr(), X, Y, m, h,
-              _ptr(send_left), _ptr(send_right), _lib.stream_handle(stream))
+    if residual is None:
+        _lib.call("smi_stencil_step", inp.data_ptr(), out.data_ptr(), X, Y, m, h,
+                  _ptr(send_left), _ptr(send_right), _lib.stream_handle(stream))
+        return
+    if residual.dtype != torch.int32 or residual.numel() != 1 or not residual.is_cuda:
+        raise ValueError("residual must be a one-element int32 device tensor")
+    _lib.call("smi_stencil_step_residual", inp.data_ptr(), out.data_ptr(), X, Y, m, h,
+              _ptr(send_left), _ptr(send_right), residual.data_ptr(), _lib.stream_handle(stream))
+
+
+def residual_value(residual: torch.Tensor) -> float:
+    """The fp32 max |out - inp| a residual word holds (synchronises)."""
+    return float(residual.cpu().numpy().view(np.float32).reshape(-1)[0])
+
+
+def solve(comm: Comm, tile: torch.Tensor, tol: float, max_steps: int, check_every: int = 20, PX: int = 1,
+          PY: int = 1, scratch: torch.Tensor | None = None, stream=None):
+    """Jacobi steps until max |x_t - x_{t-1}| over the global grid is <= tol
+    at a check point (every check_every steps and at max_steps), or max_steps
+    (smi_stencil_solve; collective, synchronises with the host at every
+    check).  Returns (result tensor -- tile or scratch --, steps, residual,
+    converged); the residual is a numpy float32 (exact), +inf if no step ran."""
+    if scratch is None:
+        scratch = torch.empty_like(tile)
+    X, Y = tile.shape
+    idx, steps, conv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    res = ctypes.c_float()
+    _lib.call("smi_stencil_solve", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
+              ctypes.c_float(tol), max_steps, check_every, _lib.stream_handle(stream, tile.get_device()),
+              ctypes.byref(idx), ctypes.byref(steps), ctypes.byref(res), ctypes.byref(conv))
+    r = np.frombuffer(bytes(res), dtype=np.float32)[0]
+    return (tile if idx.value == 0 else scratch), steps.value, r, bool(conv.value)
 
 
 def run(comm: Comm, tile: torch.Tensor, timesteps: int, PX: int, PY: int,

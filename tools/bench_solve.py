@@ -1,0 +1,169 @@
+#!/usr/bin/env python3
+"""What a convergence check costs (profiles/solve/).
+
+Two measurements at 8192^2 on one GPU, appended as JSON lines to --out:
+
+  --mode step   one library (--lib, default this tree's), loaded on its own
+                with ctypes: smi_stencil_step timed over windows of --steps
+                back-to-back single steps, --reps windows, device events
+                around each window; if the library has it, the same for
+                smi_stencil_step_residual, and for the unfused check a caller
+                would otherwise write (a plain step plus a max|a - b| pass
+                over both buffers).  Run it once per library -- the parent
+                commit's and this tree's -- alternating, in fresh processes:
+                two copies of the library in one process would share symbols.
+  --mode solve  smi_stencil_solve against smi_stencil_run for the same number
+                of steps (tol = 0 is never met on a random grid), check_every
+                20, 100 and 400, host clock around the call and a stream
+                synchronise; ms per step for both and the cost of one check
+                (the single residual step, reduce, bcast, 4 bytes back and the
+                host synchronise) = (solve - run) / checks.
+
+Not part of bench.py; a GPU is required.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def summary(ms: list[float]) -> dict:
+    s = sorted(ms)
+    return dict(median_ms=statistics.median(s), min_ms=s[0], max_ms=s[-1], stdev_ms=statistics.pstdev(s),
+                p10_ms=s[len(s) // 10], p90_ms=s[-1 - len(s) // 10], reps=len(s))
+
+
+def emit(out: str, rec: dict) -> None:
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    line = json.dumps(rec)
+    print(line, flush=True)
+    with open(out, "a") as f:
+        f.write(line + "\n")
+
+
+def mode_step(args) -> None:
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_solve needs a GPU")
+    from smi_amd import build
+    path = args.lib or build.lib_path()
+    lib = ctypes.CDLL(path)      # torch's HIP runtime is loaded already
+    P, I = ctypes.c_void_p, ctypes.c_int
+    lib.smi_stencil_step.argtypes = [P, P, I, I, ctypes.POINTER(I), ctypes.POINTER(P), P, P, P]
+    fused = getattr(lib, "smi_stencil_step_residual", None)
+    if fused is not None:
+        fused.argtypes = [P, P, I, I, ctypes.POINTER(I), ctypes.POINTER(P), P, P, P, P]
+    N = args.size
+    torch.manual_seed(0)
+    a = torch.rand((N, N), device="cuda")
+    b = torch.empty_like(a)
+    word = torch.zeros(1, dtype=torch.int32, device="cuda")
+    mode = (I * 4)(0, 0, 0, 0)
+    halo = (P * 4)()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def plain(x, y):
+        rc = lib.smi_stencil_step(x.data_ptr(), y.data_ptr(), N, N, mode, halo, None, None, stream)
+        assert rc == 0, rc
+
+    def with_residual(x, y):
+        rc = fused(x.data_ptr(), y.data_ptr(), N, N, mode, halo, None, None, word.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def unfused(x, y):
+        plain(x, y)
+        torch.max(torch.abs(y - x))     # what a caller writes without the fused step
+
+    variants = [("plain_step", plain)]
+    if fused is not None:
+        variants.append(("fused_residual_step", with_residual))
+    variants.append(("plain_step_plus_difference_pass", unfused))
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = {name: [] for name, _ in variants}
+    for name, fn in variants:           # warm every variant
+        for _ in range(args.steps):
+            fn(a, b)
+            a, b = b, a
+    torch.cuda.synchronize()
+    for _ in range(args.reps):          # variants alternate inside every repetition
+        for name, fn in variants:
+            ev0.record()
+            for _ in range(args.steps):
+                fn(a, b)
+                a, b = b, a
+            ev1.record()
+            ev1.synchronize()
+            times[name].append(ev0.elapsed_time(ev1) / args.steps)
+    for name, _ in variants:
+        emit(args.out, dict(kind="step", label=args.label, variant=name, size=N, steps_per_window=args.steps,
+                            unit="ms per step",
+                            **summary(times[name])))
+
+
+def mode_solve(args) -> None:
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_solve needs a GPU")
+    import smi_amd
+    from smi_amd import stencil
+    N, T = args.size, args.total_steps
+    comm = smi_amd.LocalGroup(1).comm(0)
+    torch.manual_seed(0)
+    src = torch.rand((N, N), device="cuda")
+    tile, scratch = torch.empty_like(src), torch.empty_like(src)
+
+    def run_once(fn) -> float:
+        tile.copy_(src)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def do_run():
+        stencil.run(comm, tile, T, 1, 1, scratch=scratch)
+
+    for ce in (20, 100, 400):
+        def do_solve():
+            _, steps, r, conv = stencil.solve(comm, tile, 0.0, T, ce, 1, 1, scratch=scratch)
+            assert steps == T and not conv, (steps, r, conv)
+
+        for fn in (do_run, do_solve):
+            run_once(fn)
+        t_run, t_solve = [], []
+        for _ in range(args.reps):      # alternating
+            t_run.append(run_once(do_run))
+            t_solve.append(run_once(do_solve))
+        checks = (T + ce - 1) // ce
+        run_s, solve_s = summary(t_run), summary(t_solve)
+        emit(args.out, dict(kind="solve_vs_run", label=args.label, size=N, steps=T, check_every=ce, checks=checks,
+                            run_ms_per_step=run_s["median_ms"] / T, solve_ms_per_step=solve_s["median_ms"] / T,
+                            per_check_overhead_ms=(solve_s["median_ms"] - run_s["median_ms"]) / checks,
+                            run_stdev_ms_per_step=run_s["stdev_ms"] / T, run=run_s, solve=solve_s))
+    comm.finalize()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--mode", choices=("step", "solve"), required=True)
+    ap.add_argument("--lib", default=None, help="step mode: the libsmi_amd.so to time (default: this tree's)")
+    ap.add_argument("--label", default="current", help="recorded with every line (e.g. parent / current)")
+    ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=200, help="step mode: single steps per timed window")
+    ap.add_argument("--total-steps", type=int, default=2000, help="solve mode: steps of every run / solve")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solve", "solve.jsonl"))
+    args = ap.parse_args()
+    (mode_step if args.mode == "step" else mode_solve)(args)
+
+
+if __name__ == "__main__":
+    main()
