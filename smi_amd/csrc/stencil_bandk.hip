@@ -9,35 +9,17 @@ namespace smi {
 
 #define SMI_BANDK_DECL(K) \
     int bandk_launch_k##K(const BandKArgs &a, int waves, hipStream_t s, hipEvent_t start, hipEvent_t stop);
-SMI_BANDK_DECL(3)
-SMI_BANDK_DECL(4)
-SMI_BANDK_DECL(5)
-SMI_BANDK_DECL(6)
-SMI_BANDK_DECL(7)
-SMI_BANDK_DECL(8)
-SMI_BANDK_DECL(9)
-SMI_BANDK_DECL(10)
-SMI_BANDK_DECL(11)
-SMI_BANDK_DECL(12)
-SMI_BANDK_DECL(13)
-SMI_BANDK_DECL(14)
-SMI_BANDK_DECL(15)
-SMI_BANDK_DECL(16)
-SMI_BANDK_DECL(17)
-SMI_BANDK_DECL(18)
-SMI_BANDK_DECL(19)
-SMI_BANDK_DECL(20)
-
+SMI_FOR_K_3_12(SMI_BANDK_DECL)
+SMI_FOR_K_13_20(SMI_BANDK_DECL)
 #define SMI_BANDL_DECL(K) \
     int bandl_launch_k##K(const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start, hipEvent_t stop);
-SMI_BANDL_DECL(13)
-SMI_BANDL_DECL(14)
-SMI_BANDL_DECL(15)
-SMI_BANDL_DECL(16)
-SMI_BANDL_DECL(17)
-SMI_BANDL_DECL(18)
-SMI_BANDL_DECL(19)
-SMI_BANDL_DECL(20)
+SMI_FOR_K_13_20(SMI_BANDL_DECL)
+// [K - SWEEPK_MIN] / [K - SWEEPD_MIN]; plan_bands refuses a K outside 3..20
+#define SMI_BANDK_ENTRY(K) bandk_launch_k##K,
+#define SMI_BANDL_ENTRY(K) bandl_launch_k##K,
+static constexpr decltype(bandk_launch_k3) *kBandK[] = {SMI_FOR_K_3_12(SMI_BANDK_ENTRY)
+                                                        SMI_FOR_K_13_20(SMI_BANDK_ENTRY)};
+static constexpr decltype(bandl_launch_k13) *kBandL[] = {SMI_FOR_K_13_20(SMI_BANDL_ENTRY)};
 
 static int compute_units() {
     static int cached[64] = {};
@@ -49,19 +31,6 @@ static int compute_units() {
         cached[dev] = cus;
     }
     return cached[dev];
-}
-
-static int launch_bandl(int K, const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    switch (K) {
-    case 13: return bandl_launch_k13(a, blocks, s, start, stop);
-    case 14: return bandl_launch_k14(a, blocks, s, start, stop);
-    case 15: return bandl_launch_k15(a, blocks, s, start, stop);
-    case 16: return bandl_launch_k16(a, blocks, s, start, stop);
-    case 17: return bandl_launch_k17(a, blocks, s, start, stop);
-    case 18: return bandl_launch_k18(a, blocks, s, start, stop);
-    case 19: return bandl_launch_k19(a, blocks, s, start, stop);
-    default: return bandl_launch_k20(a, blocks, s, start, stop);
-    }
 }
 
 int plan_bands(int K, BandKArgs *ap, bool lean) {
@@ -122,7 +91,6 @@ int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t st
         SMI_TRY(prof_launch(SMI_PROF_STENCIL_EDGE, &tok, K, 0.0, &start, &kstop));
         after = stop;
     }
-    int rc = SMI_SUCCESS;
     if (lean) {
         // the lean kernel beside the interior: one workgroup (4 waves) per CU
         // at most, fewer when max_waves asks for fewer
@@ -130,33 +98,11 @@ int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t st
         SMI_ARG_CHECK(cus > 0, "bandl: compute-unit query failed");
         int blocks = std::min(cus, (segs + 3) / 4);
         if (max_waves > 0) blocks = std::min(blocks, std::max(1, max_waves / 4));
-        SMI_TRY(launch_bandl(K, a, blocks, s, start, kstop));
-        if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
-        return SMI_SUCCESS;
+        SMI_TRY(kBandL[K - SWEEPD_MIN](a, blocks, s, start, kstop));
+    } else {
+        SMI_TRY(kBandK[K - SWEEPK_MIN](a, n, s, start, kstop));
     }
-    switch (K) {
-    case 3: rc = bandk_launch_k3(a, n, s, start, kstop); break;
-    case 4: rc = bandk_launch_k4(a, n, s, start, kstop); break;
-    case 5: rc = bandk_launch_k5(a, n, s, start, kstop); break;
-    case 6: rc = bandk_launch_k6(a, n, s, start, kstop); break;
-    case 7: rc = bandk_launch_k7(a, n, s, start, kstop); break;
-    case 8: rc = bandk_launch_k8(a, n, s, start, kstop); break;
-    case 9: rc = bandk_launch_k9(a, n, s, start, kstop); break;
-    case 10: rc = bandk_launch_k10(a, n, s, start, kstop); break;
-    case 11: rc = bandk_launch_k11(a, n, s, start, kstop); break;
-    case 12: rc = bandk_launch_k12(a, n, s, start, kstop); break;
-    case 13: rc = bandk_launch_k13(a, n, s, start, kstop); break;
-    case 14: rc = bandk_launch_k14(a, n, s, start, kstop); break;
-    case 15: rc = bandk_launch_k15(a, n, s, start, kstop); break;
-    case 16: rc = bandk_launch_k16(a, n, s, start, kstop); break;
-    case 17: rc = bandk_launch_k17(a, n, s, start, kstop); break;
-    case 18: rc = bandk_launch_k18(a, n, s, start, kstop); break;
-    case 19: rc = bandk_launch_k19(a, n, s, start, kstop); break;
-    default: rc = bandk_launch_k20(a, n, s, start, kstop); break;
-    }
-    SMI_TRY(rc);
     if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
-    (void)tok;
     return SMI_SUCCESS;
 }
 

@@ -132,6 +132,19 @@ struct SweepKArgs {
     int gT, gB, gL, gR;
 };
 constexpr int SWEEPK_MIN = 3, SWEEPK_MAX = 12;
+// The K of the per-K instantiation units (stencilk_k / stencild_k / bandk_k
+// <K>.hip): the host sides declare the units' entry points and build their
+// dispatch tables, indexed by K - first, from these two lists.
+#define SMI_FOR_K_3_12(X) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
+#define SMI_FOR_K_13_20(X) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
+// a sweep's output rectangle: float4-aligned columns, inside the tile
+inline int check_sweep_rect(const char *who, const SweepKArgs &a) {
+    SMI_ARG_CHECK(a.cols % 4 == 0 && a.col_lo % 4 == 0 && a.col_hi % 4 == 0,
+                  std::string(who) + ": columns not float4 aligned");
+    SMI_ARG_CHECK(a.row_lo >= 0 && a.row_hi <= a.rows && a.col_lo >= 0 && a.col_hi <= a.cols,
+                  std::string(who) + ": output rectangle outside the tile");
+    return SMI_SUCCESS;
+}
 // Lanes per 64-lane window side that never store (the window apron is 4x
 // as many columns, >= K): 4 for K >= 9 (224 stored columns, line-aligned
 // stores), else the minimal ceil(K / 4).

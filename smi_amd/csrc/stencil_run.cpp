@@ -125,161 +125,170 @@ static int interior_stream(Comm *c, hipStream_t user, hipStream_t *out, bool *ow
     return SMI_SUCCESS;
 }
 
-// Depth-1 exchange: new first/last row -> rank above/below, packed first/last
-// column -> left/right rank; the four halo vectors come back from them.
-static int exchange1(Comm *c, const Neighbours &nb, const float *tile, int rows, int cols, float *h_top,
-                     float *h_bot, float *h_left, float *h_right, const float *s_left, const float *s_right,
-                     hipStream_t s) {
-    Transport *tp = c->transport.get();
-    const size_t rb = (size_t)cols * sizeof(float), cb = (size_t)rows * sizeof(float);
-    Group grp(tp);
-    SMI_TRY(grp.begin(s));
-    if (nb.top >= 0) {
-        SMI_TRY(tp->send(tile, rb, nb.top));
-        SMI_TRY(tp->recv(h_top, rb, nb.top));
-    }
-    if (nb.bottom >= 0) {
-        SMI_TRY(tp->send(tile + (size_t)(rows - 1) * cols, rb, nb.bottom));
-        SMI_TRY(tp->recv(h_bot, rb, nb.bottom));
-    }
-    if (nb.left >= 0) {
-        SMI_TRY(tp->send(s_left, cb, nb.left));
-        SMI_TRY(tp->recv(h_left, cb, nb.left));
-    }
-    if (nb.right >= 0) {
-        SMI_TRY(tp->send(s_right, cb, nb.right));
-        SMI_TRY(tp->recv(h_right, cb, nb.right));
-    }
-    return grp.end();
+// One rank's tile during a run: what every phase reads, and the ping-pong
+// index its passes flip.
+struct Tile {
+    Comm *c;
+    float *buf[2];
+    int rows, cols;
+    Neighbours nb;
+    int side_mask;        // bit 0..3: neighbour on side top, bottom, left, right
+    unsigned int *resid;  // the checked step of smi_stencil_solve, else nullptr
+    int cur;              // index of the buffer holding the current state
+    const float *in() const { return buf[cur]; }
+    float *out() const { return buf[cur ^ 1]; }
+    bool has(int side) const { return (side_mask >> side) & 1; }
+};
+
+// One halo exchange: up to eight messages in the order top, bottom, left,
+// right, tl, tr, bl, br (peer < 0: no such neighbour).  The kernels see the
+// receive side as const; the transport writes it.
+struct HaloMsg {
+    int peer;
+    const float *send, *recv;
+    size_t bytes;
+};
+struct HaloMsgs {
+    HaloMsg m[8];
+};
+
+// the one place a receive-side `const float *` of the device-facing halo
+// structs becomes the transport's writable buffer
+static void *recv_buf(const HaloMsg &m) { return const_cast<float *>(m.recv); }
+
+// The side messages at depth d rows / dc columns: the tile's first / last d
+// rows are sent straight from it, its packed first / last dc columns from the
+// staging; no corners (the depth-2 and depth-K phases add theirs).
+static HaloMsgs side_msgs(const Tile &t, const float *tile, int d, int dc, const float *top, const float *bot,
+                          const float *left, const float *right, const float *send_left, const float *send_right) {
+    const size_t rb = (size_t)d * t.cols * sizeof(float), cb = (size_t)t.rows * dc * sizeof(float);
+    HaloMsgs x;
+    x.m[0] = {t.nb.top, tile, top, rb};
+    x.m[1] = {t.nb.bottom, tile + (size_t)(t.rows - d) * t.cols, bot, rb};
+    x.m[2] = {t.nb.left, send_left, left, cb};
+    x.m[3] = {t.nb.right, send_right, right, cb};
+    for (int k = 4; k < 8; ++k) x.m[k] = {-1, nullptr, nullptr, 0};
+    return x;
 }
 
 // Depth-2 exchange (once per pair of steps): two rows / two columns per
 // side neighbour, one corner cell per diagonal neighbour.
-struct Halo2Buf {
-    float *top2, *bot2, *left2, *right2, *corner, *send_left2, *send_right2, *send_corner;
-    // Every pointer is a valid allocation, also for sides without a
-    // neighbour (their values are never used; the kernels rely on it).
-    Halo2 view() const {
-        Halo2 h;
-        h.top2 = top2;
-        h.bot2 = bot2;
-        h.left2 = left2;
-        h.right2 = right2;
-        h.corner = corner;
-        h.send_left2 = send_left2;
-        h.send_right2 = send_right2;
-        h.send_corner = send_corner;
-        return h;
-    }
-};
-
-static int exchange2(Comm *c, const Neighbours &nb, const float *tile, int rows, int cols, const Halo2Buf &h,
-                     hipStream_t s) {
-    Transport *tp = c->transport.get();
-    const size_t rb = 2 * (size_t)cols * sizeof(float), cb = 2 * (size_t)rows * sizeof(float);
-    Group grp(tp);
-    SMI_TRY(grp.begin(s));
-    if (nb.top >= 0) {
-        SMI_TRY(tp->send(tile, rb, nb.top));
-        SMI_TRY(tp->recv(h.top2, rb, nb.top));
-    }
-    if (nb.bottom >= 0) {
-        SMI_TRY(tp->send(tile + (size_t)(rows - 2) * cols, rb, nb.bottom));
-        SMI_TRY(tp->recv(h.bot2, rb, nb.bottom));
-    }
-    if (nb.left >= 0) {
-        SMI_TRY(tp->send(h.send_left2, cb, nb.left));
-        SMI_TRY(tp->recv(h.left2, cb, nb.left));
-    }
-    if (nb.right >= 0) {
-        SMI_TRY(tp->send(h.send_right2, cb, nb.right));
-        SMI_TRY(tp->recv(h.right2, cb, nb.right));
-    }
-    const int diag[4] = {nb.tl, nb.tr, nb.bl, nb.br};
-    for (int k = 0; k < 4; ++k) {
-        if (diag[k] < 0) continue;
-        SMI_TRY(tp->send(h.send_corner + k, sizeof(float), diag[k]));
-        SMI_TRY(tp->recv(h.corner + k, sizeof(float), diag[k]));
-    }
-    return grp.end();
+static HaloMsgs msgs2(const Tile &t, const float *tile, const Halo2 &h) {
+    HaloMsgs x = side_msgs(t, tile, 2, 2, h.top2, h.bot2, h.left2, h.right2, h.send_left2, h.send_right2);
+    const int diag[4] = {t.nb.tl, t.nb.tr, t.nb.bl, t.nb.br};
+    for (int k = 0; k < 4; ++k) x.m[4 + k] = {diag[k], h.send_corner + k, h.corner + k, sizeof(float)};
+    return x;
 }
 
 // Depth-K exchange (once per K steps): K rows / KC = kc_of(K) columns per
 // side neighbour, one K x KC block per diagonal neighbour.
-struct HaloKBuf {
-    float *top, *bot, *left, *right, *send_left, *send_right;
-    float *corner[4], *send_corner[4];
-    HaloK view() const {
-        HaloK h;
-        h.top = top;
-        h.bot = bot;
-        h.left = left;
-        h.right = right;
-        h.send_left = send_left;
-        h.send_right = send_right;
-        for (int k = 0; k < 4; ++k) {
-            h.corner[k] = corner[k];
-            h.send_corner[k] = send_corner[k];
-        }
-        return h;
-    }
-};
+static HaloMsgs msgsk(const Tile &t, const float *tile, int K, const HaloK &h) {
+    HaloMsgs x = side_msgs(t, tile, K, kc_of(K), h.top, h.bot, h.left, h.right, h.send_left, h.send_right);
+    const int diag[4] = {t.nb.tl, t.nb.tr, t.nb.bl, t.nb.br};
+    const size_t kb = (size_t)K * kc_of(K) * sizeof(float);
+    for (int k = 0; k < 4; ++k) x.m[4 + k] = {diag[k], h.send_corner[k], h.corner[k], kb};
+    return x;
+}
 
-static int exchangek(Comm *c, const Neighbours &nb, const float *tile, int rows, int cols, int K, const HaloKBuf &h,
-                     hipStream_t s) {
+// Posts the messages in one transport group, each peer's send before its
+// receive.  depth_k: the exchange of a K-step phase (the rehearsal switches
+// act on that one only).
+static int exchange(Comm *c, const HaloMsgs &x, bool depth_k, hipStream_t s) {
     Transport *tp = c->transport.get();
 #ifdef SMI_LOOPBACK_REHEARSAL
-    if (getenv("SMI_LOOPBACK_NOXCHG")) return SMI_SUCCESS;  // rehearsal: price bands + interior alone
-#endif
-    const int KC = kc_of(K);
-    const size_t rb = (size_t)K * cols * sizeof(float), cb = (size_t)rows * KC * sizeof(float);
-    const size_t kb = (size_t)K * KC * sizeof(float);
-#ifdef SMI_LOOPBACK_REHEARSAL
-    if (getenv("SMI_LOOPBACK_FUSED") && nb.top == 0 && nb.left == 0 && nb.tl == 0) {
-        // rehearsal: the same 8 messages as one copy kernel (like one RCCL group)
-        const void *src[8] = {tile, tile + (size_t)(rows - K) * cols, h.send_left, h.send_right,
-                              h.send_corner[0], h.send_corner[1], h.send_corner[2], h.send_corner[3]};
-        void *dst[8] = {h.bot, h.top, h.right, h.left, h.corner[3], h.corner[2], h.corner[1], h.corner[0]};
-        const size_t by[8] = {rb, rb, cb, cb, kb, kb, kb, kb};
-        return launch_copies(src, dst, by, 8, s);
-    }
-    if (const char *hv = getenv("SMI_LOOPBACK_HEAVY")) {
-        if (nb.top == 0 && nb.left == 0 && nb.tl == 0) {
-            // rehearsal: one copy kernel with rcclGenericKernel's footprint,
-            // SMI_LOOPBACK_HEAVY workgroups (RCCL's channels)
-            const void *src[8] = {tile, tile + (size_t)(rows - K) * cols, h.send_left, h.send_right,
-                                  h.send_corner[0], h.send_corner[1], h.send_corner[2], h.send_corner[3]};
-            void *dst[8] = {h.bot, h.top, h.right, h.left, h.corner[3], h.corner[2], h.corner[1], h.corner[0]};
-            const size_t by[8] = {rb, rb, cb, cb, kb, kb, kb, kb};
-            return launch_heavy_copies(src, dst, by, 8, atoi(hv), s);
+    if (depth_k && getenv("SMI_LOOPBACK_NOXCHG")) return SMI_SUCCESS;  // rehearsal: price bands + interior alone
+    const char *fused = getenv("SMI_LOOPBACK_FUSED"), *heavy = getenv("SMI_LOOPBACK_HEAVY");
+    if (depth_k && (fused || heavy) && x.m[0].peer == 0 && x.m[2].peer == 0 && x.m[4].peer == 0) {
+        // rehearsal, own neighbour on every side: the same 8 messages as one
+        // copy kernel (like one RCCL group), message i landing in the receive
+        // buffer of the opposite message; HEAVY: with rcclGenericKernel's
+        // footprint, SMI_LOOPBACK_HEAVY workgroups (RCCL's channels)
+        const void *src[8];
+        void *dst[8];
+        size_t by[8];
+        for (int i = 0; i < 8; ++i) {
+            src[i] = x.m[i].send;
+            dst[i] = recv_buf(x.m[i < 4 ? i ^ 1 : 11 - i]);
+            by[i] = x.m[i].bytes;
         }
+        return fused ? launch_copies(src, dst, by, 8, s) : launch_heavy_copies(src, dst, by, 8, atoi(heavy), s);
     }
 #endif
     Group grp(tp);
     SMI_TRY(grp.begin(s));
-    if (nb.top >= 0) {
-        SMI_TRY(tp->send(tile, rb, nb.top));
-        SMI_TRY(tp->recv(h.top, rb, nb.top));
-    }
-    if (nb.bottom >= 0) {
-        SMI_TRY(tp->send(tile + (size_t)(rows - K) * cols, rb, nb.bottom));
-        SMI_TRY(tp->recv(h.bot, rb, nb.bottom));
-    }
-    if (nb.left >= 0) {
-        SMI_TRY(tp->send(h.send_left, cb, nb.left));
-        SMI_TRY(tp->recv(h.left, cb, nb.left));
-    }
-    if (nb.right >= 0) {
-        SMI_TRY(tp->send(h.send_right, cb, nb.right));
-        SMI_TRY(tp->recv(h.right, cb, nb.right));
-    }
-    const int diag[4] = {nb.tl, nb.tr, nb.bl, nb.br};
-    for (int k = 0; k < 4; ++k) {
-        if (diag[k] < 0) continue;
-        SMI_TRY(tp->send(h.send_corner[k], kb, diag[k]));
-        SMI_TRY(tp->recv(h.corner[k], kb, diag[k]));
+    for (const HaloMsg &m : x.m) {
+        if (m.peer < 0) continue;
+        SMI_TRY(tp->send(m.send, m.bytes, m.peer));
+        SMI_TRY(tp->recv(recv_buf(m), m.bytes, m.peer));
     }
     return grp.end();
+}
+
+// Halo staging.  Depth 2 (its inner row/column doubles as the depth-1
+// halo): top2 | bot2 | left2 | right2 | corner(4) | send_left2 |
+// send_right2 | send_corner(4); then depth K (16-byte aligned): top | bot
+// (K x cols) | left | right | send_left | send_right (rows x KC, [row][k])
+// | 4 + 4 K x KC corners.  The regions are sized for the deepest phase; a
+// shallower phase (the remainder pass) lays its depth out densely from
+// the start of each region.  Every pointer is a valid allocation, also for
+// sides without a neighbour (their values are never used; the kernels rely
+// on it).
+static size_t halo2_elems(int rows, int cols) { return (4 * (size_t)cols + 8 * (size_t)rows + 8 + 3) / 4 * 4; }
+static size_t halok_elems(int rows, int cols, int kmax) {
+    const size_t kc = kc_of(kmax);
+    return kmax ? 2 * (size_t)kmax * cols + 4 * (size_t)rows * kc + 8 * (size_t)kmax * kc : 0;
+}
+
+static Halo2 halo2_layout(float *base, int rows, int cols) {
+    const size_t c2 = 2 * (size_t)cols, r2 = 2 * (size_t)rows;
+    float *left2 = base + 2 * c2, *corner = left2 + 2 * r2, *send_left2 = corner + 4;
+    Halo2 h;
+    h.top2 = base;
+    h.bot2 = base + c2;
+    h.left2 = left2;
+    h.right2 = left2 + r2;
+    h.corner = corner;
+    h.send_left2 = send_left2;
+    h.send_right2 = send_left2 + r2;
+    h.send_corner = send_left2 + 2 * r2;
+    return h;
+}
+
+static HaloK halok_layout(float *base, int rows, int cols, int kmax) {
+    const size_t rb = (size_t)kmax * cols, cb = (size_t)rows * kc_of(kmax), kb = (size_t)kmax * kc_of(kmax);
+    float *left = base + 2 * rb, *corners = left + 4 * cb;
+    HaloK h;
+    h.top = base;
+    h.bot = base + rb;
+    h.left = left;
+    h.right = left + cb;
+    h.send_left = left + 2 * cb;
+    h.send_right = left + 3 * cb;
+    for (int k = 0; k < 4; ++k) {
+        h.corner[k] = corners + k * kb;
+        h.send_corner[k] = corners + (4 + k) * kb;
+    }
+    return h;
+}
+
+// K-step passes: the interior sweep of a tile with neighbours on side_mask
+// (bit 0..3: top, bottom, left, right) stays K rows / 4*ceil(K/4) columns
+// clear of every halo-facing side (the band kernel computes those bands
+// beside it); global edges are handled inside the sweep (stencilk.h).
+static SweepKArgs interior_rect(int rows, int cols, int K, int side_mask) {
+    const int kc = kc_of(K);
+    SweepKArgs a{};
+    a.rows = rows;
+    a.cols = cols;
+    a.row_lo = (side_mask & 1) ? K : 0;
+    a.row_hi = (side_mask & 2) ? rows - K : rows;
+    a.col_lo = (side_mask & 4) ? kc : 0;
+    a.col_hi = (side_mask & 8) ? cols - kc : cols;
+    a.gT = !(side_mask & 1);
+    a.gB = !(side_mask & 2);
+    a.gL = !(side_mask & 4);
+    a.gR = !(side_mask & 8);
+    return a;
 }
 
 static int ensure_halo(Comm *c, size_t elems) {
@@ -343,13 +352,9 @@ static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
     }
     if (K > SWEEPK_MAX) {
         // deep passes (stencild.h) need a tall enough sweep rectangle (a
-        // multi-rank interior loses K rows per side with a neighbour)
-        SweepKArgs probe{};
-        probe.rows = rows;
-        probe.cols = cols;
-        probe.row_hi = multi ? rows - 2 * K : rows;
-        probe.col_hi = cols;
-        if (!sweepd_fits(K, probe)) K = SWEEPK_MAX;
+        // multi-rank interior loses K rows per side with a neighbour; the
+        // plan does not know which sides have one and assumes both)
+        if (!sweepd_fits(K, interior_rect(rows, cols, K, multi ? 1 | 2 : 0))) K = SWEEPK_MAX;
     }
     if (cols < 8 || K < SWEEPK_MIN) K = 0;
     int rest = timesteps;
@@ -371,6 +376,315 @@ static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
     add(1, rest);
     return p;
 }
+
+// single-step / pair arguments (halo views and buffers set by the phases)
+static SweepArgs step_args(const Tile &t) {
+    SweepArgs a{};
+    a.rows = t.rows;
+    a.cols = t.cols;
+    for (int k = 0; k < 4; ++k) a.mode[k] = t.has(k) ? SMI_SIDE_HALO : SMI_SIDE_COPY;
+    return a;
+}
+static Sweep2Args pair_args(const Tile &t) {
+    Sweep2Args a2{};
+    a2.rows = t.rows;
+    a2.cols = t.cols;
+    for (int k = 0; k < 4; ++k) a2.skip[k] = t.has(k);
+    return a2;
+}
+
+// The single-tile run: no halos, no exchange, no events.
+static int run_single(Tile &t, const Plan &plan, hipStream_t s) {
+    SweepArgs a = step_args(t);
+    Sweep2Args a2 = pair_args(t);
+    for (int ph = 0; ph < plan.nph; ++ph) {
+        const int K = plan.k[ph];
+        SweepKArgs ak = interior_rect(t.rows, t.cols, K, 0);
+        for (int p = 0; p < plan.n[ph]; ++p, t.cur ^= 1) {
+            if (K >= SWEEPK_MIN) {
+                ak.in = t.in();
+                ak.out = t.out();
+                SMI_TRY(launch_sweepk(K, ak, s));
+            } else if (K == 2) {
+                a2.in = t.in();
+                a2.out = t.out();
+                SMI_TRY(launch_sweep2(a2, s));
+            } else {
+                a.in = t.in();
+                a.out = t.out();
+                SMI_TRY(launch_sweep_res(a, t.resid, s));
+            }
+        }
+    }
+    return SMI_SUCCESS;
+}
+
+// Who records a pass's two ordering events.  ByDispatch (K-step passes): the
+// ring / interior launches are handed the event as `stop` and record it by
+// their own dispatch (no marker packets between kernels; ~4 us per pass,
+// tools/streambench).  AfterLaunch (pairs, single steps): their kernels
+// ignore `stop`, and pass() records the event after them.
+enum class Events { ByDispatch, AfterLaunch };
+
+// The pass scheduler of a multi-rank run.
+// Schedule (two streams, no host synchronisation between passes):
+//   comm stream : [wait interior(t-1)] band(t) -> rec E_edge(t) -> exchange(t)
+//   main stream : [wait E_edge(t-1)] interior(t)    -> rec E_int(t)
+// The band kernel (the depth-K bands; the depth-2 / depth-1 phases use
+// their ring / edge kernels) reads in(t) (interior cells from interior(t-1),
+// halo-facing cells from its own predecessor) and the halos of
+// exchange(t-1); the interior reads only in(t), never a halo vector, so
+// neither the halo-facing cells nor the xGMI exchange sit on its path.
+// Each phase (K-step passes, the remainder pass, pairs, singles) starts
+// from halos of the current state: the neighbours' current edges (for
+// the first phase the reference's artificial timestep t=0,
+// stencil_smi.cl:26-29,183-224).
+struct PassSched {
+    hipStream_t s, cs;  // main (interior) stream, comm stream
+    hipEvent_t ev_edge, ev_int, ev_edge_alt;
+    bool overlap, host_join;
+    int kpass;             // K-step passes of the current phase
+    hipEvent_t last_band;  // completion of the phase's last band kernel (host join)
+
+    int phase_start() {
+        SMI_HIP_CHECK(hipEventRecord(ev_int, s));
+        SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
+        return SMI_SUCCESS;
+    }
+
+    // One pass of a phase: bands (comm stream) + interior (main stream).
+    // ring(st, stop) / interior(st, stop): the launches, stop (nullable) as
+    // under Events; xchg(tile, st): the halo exchange of the pass's result
+    // `next` (nullptr: the phase's last pass, whose result the next phase
+    // exchanges at the depth it needs).
+    template <class Ring, class Interior, class Xchg>
+    int pass(const Ring &ring, const Interior &interior, const Xchg &xchg, const float *next, Events ev) {
+        const bool carried = ev == Events::ByDispatch;
+        if (overlap && carried && host_join) {
+            // K-step passes, host-observed join (see join_band above):
+            // band(t) carries ev_band[t & 1]; interior(t) follows band(t-1)
+            // with no wait packet when the host has seen band(t-1) finish
+            hipEvent_t ev_cur = (kpass & 1) ? ev_edge_alt : ev_edge, ev_prev = (kpass & 1) ? ev_edge : ev_edge_alt;
+            SMI_TRY(ring(cs, ev_cur));
+            rehearsal_stall(kpass);
+            if (kpass > 0) SMI_TRY(join_band(ev_prev));
+            SMI_TRY(interior(s, ev_int));
+            if (next) SMI_TRY(xchg(next, cs));
+            SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
+            last_band = ev_cur;
+            ++kpass;
+        } else if (overlap) {
+            // Overlapped, the main stream waits for the bands on the device.
+            // The interior is enqueued before the exchange: posting the
+            // transport's sends/receives costs host time (RCCL group, or
+            // event + copy per message in-process) that must not delay the
+            // interior's launch -- the trace of an interior rank showed the
+            // main stream idle ~100 us per pass behind the exchange calls.
+            SMI_TRY(ring(cs, carried ? ev_edge : nullptr));
+            if (!carried) SMI_HIP_CHECK(hipEventRecord(ev_edge, cs));
+            if (carried) {
+                rehearsal_stall(kpass);
+                ++kpass;
+            }
+            SMI_TRY(interior(s, carried ? ev_int : nullptr));
+            if (!carried) SMI_HIP_CHECK(hipEventRecord(ev_int, s));
+            SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_edge, 0));
+            if (next) SMI_TRY(xchg(next, cs));
+            SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
+        } else {
+            // No overlap: everything but the exchange on the main stream.
+            SMI_HIP_CHECK(hipEventRecord(ev_edge, cs));
+            SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_edge, 0));
+            SMI_TRY(ring(s, nullptr));
+            SMI_TRY(interior(s, nullptr));
+            SMI_HIP_CHECK(hipEventRecord(ev_int, s));
+            SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
+            if (next) SMI_TRY(xchg(next, cs));
+        }
+        return SMI_SUCCESS;
+    }
+};
+
+// ---- K steps per pass (depth-K halos)
+static int k_passes(Tile &t, PassSched &sc, int K, int npass, const HaloK &hk) {
+    SweepKArgs ak = interior_rect(t.rows, t.cols, K, t.side_mask);
+    BandKArgs bk{};
+    bk.rows = t.rows;
+    bk.cols = t.cols;
+    for (int k = 0; k < 4; ++k) bk.has[k] = t.has(k);
+    bk.pack = t.side_mask != 0;
+    bk.h = hk;
+    auto ring = [&](hipStream_t st, hipEvent_t stop) { return launch_bandk(K, bk, g_tune.band_reserve, st, stop); };
+    auto interior = [&](hipStream_t st, hipEvent_t stop) {
+        return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop);
+    };
+    auto xchgk = [&](const float *tile, hipStream_t st) { return exchange(t.c, msgsk(t, tile, K, hk), true, st); };
+    SMI_TRY(launch_packk(t.in(), t.rows, t.cols, K, hk, sc.cs));
+    SMI_TRY(xchgk(t.in(), sc.cs));
+    sc.kpass = 0;
+    for (int p = 0; p < npass; ++p, t.cur ^= 1) {
+        bk.in = ak.in = t.in();
+        bk.out = ak.out = t.out();
+        SMI_TRY(sc.pass(ring, interior, xchgk, p < npass - 1 ? ak.out : nullptr, Events::ByDispatch));
+    }
+    // whatever runs next on the main stream reads the last bands:
+    // joined on the host as well (no wait packet on the interior
+    // stream, see join_band)
+    if (sc.host_join && sc.last_band) SMI_TRY(join_band(sc.last_band));
+    return SMI_SUCCESS;
+}
+
+// ---- pairs of steps (depth-2 halos)
+static int pair_passes(Tile &t, PassSched &sc, int npass, const Halo2 &h2) {
+    Sweep2Args a2 = pair_args(t);
+    auto ring = [&](hipStream_t st, hipEvent_t) { return launch_ring2(a2, h2, st); };
+    auto interior = [&](hipStream_t st, hipEvent_t) { return launch_sweep2(a2, st); };
+    auto xchg2 = [&](const float *tile, hipStream_t st) { return exchange(t.c, msgs2(t, tile, h2), false, st); };
+    SMI_TRY(launch_pack2(t.in(), t.rows, t.cols, h2, sc.cs));
+    SMI_TRY(xchg2(t.in(), sc.cs));
+    for (int p = 0; p < npass; ++p, t.cur ^= 1) {
+        a2.in = t.in();
+        a2.out = t.out();
+        SMI_TRY(sc.pass(ring, interior, xchg2, p < npass - 1 ? a2.out : nullptr, Events::AfterLaunch));
+    }
+    return SMI_SUCCESS;
+}
+
+// ---- single steps (depth-1 halos: the inner row / column of the depth-2
+// staging -- row -1, row X, col -1, col Y -- and the packed depth-1 sends)
+static int single_steps(Tile &t, PassSched &sc, int npass, const Halo2 &h2) {
+    SweepArgs a = step_args(t);
+    a.halo[0] = h2.top2 + t.cols;
+    a.halo[1] = h2.bot2;
+    a.halo[2] = h2.left2 + t.rows;
+    a.halo[3] = h2.right2;
+    float *s_left = h2.send_left2 + t.rows, *s_right = h2.send_right2;  // staging only
+    a.send_left = t.nb.left >= 0 ? s_left : nullptr;
+    a.send_right = t.nb.right >= 0 ? s_right : nullptr;
+    SweepArgs inner = a;  // interior launch: halo-facing sides left to the edge kernel
+    for (int k = 0; k < 4; ++k)
+        if (inner.mode[k] == SMI_SIDE_HALO) inner.mode[k] = SMI_SIDE_SKIP;
+    inner.send_left = inner.send_right = nullptr;
+    auto edge = [&](hipStream_t st, hipEvent_t) { return launch_edge_res(a, t.side_mask, t.resid, st); };
+    auto interior = [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(inner, t.resid, st); };
+    // without overlap the full sweep reads the halos itself
+    auto no_edge = [&](hipStream_t, hipEvent_t) { return (int)SMI_SUCCESS; };
+    auto full = [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(a, t.resid, st); };
+    auto xchg1 = [&](const float *tile, hipStream_t st) {
+        const HaloMsgs x = side_msgs(t, tile, 1, 1, a.halo[0], a.halo[1], a.halo[2], a.halo[3], s_left, s_right);
+        return exchange(t.c, x, false, st);
+    };
+    SMI_TRY(launch_pack_cols(t.in(), t.rows, t.cols, a.send_left, a.send_right, sc.cs));
+    SMI_TRY(xchg1(t.in(), sc.cs));
+    for (int p = 0; p < npass; ++p, t.cur ^= 1) {
+        a.in = inner.in = t.in();
+        a.out = inner.out = t.out();
+        const float *next = p < npass - 1 ? a.out : nullptr;
+        if (sc.overlap)
+            SMI_TRY(sc.pass(edge, interior, xchg1, next, Events::AfterLaunch));
+        else
+            SMI_TRY(sc.pass(no_edge, full, xchg1, next, Events::AfterLaunch));
+    }
+    return SMI_SUCCESS;
+}
+
+// The multi-rank run: streams and events, the phases, the join back to the
+// caller's stream.
+static int run_multi(Tile &t, const Plan &plan, hipStream_t user) {
+    Comm *c = t.c;
+    PassSched sc{};
+    sc.s = user;
+    sc.cs = c->comm_stream;
+    hipEvent_t ev_fin;
+    SMI_TRY(comm_event(c, 0, &sc.ev_edge));
+    SMI_TRY(comm_event(c, 1, &sc.ev_int));
+    SMI_TRY(comm_event(c, 2, &sc.ev_edge_alt));
+    SMI_TRY(comm_event(c, 4, &ev_fin));
+    sc.overlap = g_tune.overlap != 0;
+    bool own_stream = false;
+    if (sc.overlap) SMI_TRY(interior_stream(c, user, &sc.s, &own_stream));
+    sc.host_join = sc.overlap && host_join_enabled();
+
+    int kmax = 0;  // deepest K-step phase (sizes the depth-K staging)
+    for (int i = 0; i < plan.nph; ++i) kmax = std::max(kmax, plan.k[i] >= SWEEPK_MIN ? plan.k[i] : 0);
+    const size_t need2 = halo2_elems(t.rows, t.cols);
+    SMI_TRY(ensure_halo(c, need2 + halok_elems(t.rows, t.cols, kmax)));
+    const Halo2 h2 = halo2_layout(c->halo, t.rows, t.cols);
+
+    for (int ph = 0; ph < plan.nph; ++ph) {
+        const int K = plan.k[ph], npass = plan.n[ph];
+        SMI_TRY(sc.phase_start());
+        if (K >= SWEEPK_MIN)
+            SMI_TRY(k_passes(t, sc, K, npass, halok_layout(c->halo + need2, t.rows, t.cols, kmax)));
+        else if (K == 2)
+            SMI_TRY(pair_passes(t, sc, npass, h2));
+        else
+            SMI_TRY(single_steps(t, sc, npass, h2));
+    }
+    // the caller's stream owns the result: join the comm stream (and the
+    // interior stream when the run had one)
+    SMI_HIP_CHECK(hipEventRecord(sc.ev_edge, sc.cs));
+    SMI_HIP_CHECK(hipStreamWaitEvent(user, sc.ev_edge, 0));
+    if (own_stream) {
+        SMI_HIP_CHECK(hipEventRecord(ev_fin, sc.s));
+        SMI_HIP_CHECK(hipStreamWaitEvent(user, ev_fin, 0));
+    }
+    return SMI_SUCCESS;
+}
+
+// the tile / grid arguments smi_stencil_run and smi_stencil_solve share
+static int check_grid(const Comm *c, const float *buf0, const float *buf1, int x_local, int y_local, int px, int py) {
+    SMI_TRY(check_tile(buf0, buf1, x_local, y_local));
+    SMI_ARG_CHECK(px >= 1 && py >= 1 && px * py == c->size, "px*py must equal the communicator size");
+    return SMI_SUCCESS;
+}
+
+static int find_comm(SMI_Comm comm, Comm **c) {
+    *c = lookup_comm(comm);
+    if (*c) return SMI_SUCCESS;
+    set_error("unknown communicator");
+    return SMI_ERR_BAD_COMM;
+}
+
+// smi_stencil_run (resid == nullptr), or -- for the checked step of
+// smi_stencil_solve -- the same schedule restricted to single steps whose
+// kernels also max-accumulate |out - in| into *resid (stencil.hip).
+static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local, int px, int py, int timesteps,
+                     SMI_Stream stream_, int *result_index, unsigned int *resid) {
+    SMI_TRY(check_grid(c, buf0, buf1, x_local, y_local, px, py));
+    SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
+    SMI_ARG_CHECK(result_index, "NULL result_index");
+    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, resid, 0};
+#ifdef SMI_LOOPBACK_REHEARSAL
+    // Timing-rehearsal build only (never the product library; built by
+    // `smi_amd/build.py --rehearsal`, driven by tools/rehearsal.py): with
+    // SMI_LOOPBACK=1 a 1x1 run is its own neighbour on every side and
+    // diagonal, so one GPU replays the full per-pass work of an interior rank
+    // of a large decomposition (band kernel, 8-way exchange through the
+    // transport, interior sweep) with the same stream schedule.  The halos
+    // then wrap around, so the numbers differ from the stencil's.
+    Neighbours &nb = t.nb;
+    if (px == 1 && py == 1 && c->size == 1 && getenv("SMI_LOOPBACK"))
+        nb.top = nb.bottom = nb.left = nb.right = nb.tl = nb.tr = nb.bl = nb.br = 0;
+#endif
+    const int side_nb[4] = {t.nb.top, t.nb.bottom, t.nb.left, t.nb.right};
+    for (int k = 0; k < 4; ++k)
+        if (side_nb[k] >= 0) t.side_mask |= 1 << k;
+
+    Plan plan;
+    if (resid) {  // single steps only
+        plan.nph = timesteps > 0;
+        plan.k[0] = 1;
+        plan.n[0] = timesteps;
+    } else {
+        plan = make_plan(t.rows, t.cols, timesteps, t.side_mask != 0);
+    }
+    *result_index = plan.passes() & 1;
+    prof_break_chain();  // markers chain only between this run's own passes
+    if (timesteps == 0) return SMI_SUCCESS;
+    return t.side_mask == 0 ? run_single(t, plan, (hipStream_t)stream_) : run_multi(t, plan, (hipStream_t)stream_);
+}
+
 
 }  // namespace smi
 
@@ -459,18 +773,7 @@ int smi_stencil_deep_geometry(int rows, int cols, int K, int side_mask, int *wav
                               int *row_blocks_edge, int *min_block_rows) {
     SMI_ARG_CHECK(rows >= 1 && cols >= 4 && cols % 4 == 0, "tile must be >= 1 x 4, cols % 4 == 0");
     SMI_ARG_CHECK(side_mask >= 0 && side_mask < 16, "side_mask: bits 0..3");
-    SweepKArgs a{};
-    a.rows = rows;
-    a.cols = cols;
-    const int kc = kc_of(K);
-    a.row_lo = (side_mask & 1) ? K : 0;
-    a.row_hi = (side_mask & 2) ? rows - K : rows;
-    a.col_lo = (side_mask & 4) ? kc : 0;
-    a.col_hi = (side_mask & 8) ? cols - kc : cols;
-    a.gT = !(side_mask & 1);
-    a.gB = !(side_mask & 2);
-    a.gL = !(side_mask & 4);
-    a.gR = !(side_mask & 8);
+    const SweepKArgs a = interior_rect(rows, cols, K, side_mask);
     SMI_ARG_CHECK(sweepd_fits(K, a), "K outside 13..20 or sweep rectangle shorter than 4K rows");
     SweepDGeom g;
     SMI_TRY(sweepd_geometry(K, a, 0, &g));
@@ -515,323 +818,10 @@ int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int tim
     return SMI_SUCCESS;
 }
 
-// smi_stencil_run (resid == nullptr), or -- for the checked step of
-// smi_stencil_solve -- the same schedule restricted to single steps whose
-// kernels also max-accumulate |out - in| into *resid (stencil.hip).
-static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local, int px, int py, int timesteps,
-                     SMI_Stream stream_, int *result_index, unsigned int *resid) {
-    SMI_TRY(check_tile(buf0, buf1, x_local, y_local));
-    SMI_ARG_CHECK(px >= 1 && py >= 1 && px * py == c->size, "px*py must equal the communicator size");
-    SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
-    SMI_ARG_CHECK(result_index, "NULL result_index");
-    hipStream_t s = (hipStream_t)stream_;
-    hipStream_t cs = c->comm_stream;
-    const int rows = x_local, cols = y_local;
-    Neighbours nb = neighbours_of(c->rank, px, py);
-#ifdef SMI_LOOPBACK_REHEARSAL
-    // Timing-rehearsal build only (never the product library; built by
-    // `smi_amd/build.py --rehearsal`, driven by tools/rehearsal.py): with
-    // SMI_LOOPBACK=1 a 1x1 run is its own neighbour on every side and
-    // diagonal, so one GPU replays the full per-pass work of an interior rank
-    // of a large decomposition (band kernel, 8-way exchange through the
-    // transport, interior sweep) with the same stream schedule.  The halos
-    // then wrap around, so the numbers differ from the stencil's.
-    if (px == 1 && py == 1 && c->size == 1 && getenv("SMI_LOOPBACK"))
-        nb.top = nb.bottom = nb.left = nb.right = nb.tl = nb.tr = nb.bl = nb.br = 0;
-#endif
-    const int side_nb[4] = {nb.top, nb.bottom, nb.left, nb.right};
-    int side_mask = 0;
-    for (int k = 0; k < 4; ++k)
-        if (side_nb[k] >= 0) side_mask |= 1 << k;
-
-    Plan plan;
-    if (resid) {  // single steps only
-        plan.nph = timesteps > 0;
-        plan.k[0] = 1;
-        plan.n[0] = timesteps;
-    } else {
-        plan = make_plan(rows, cols, timesteps, side_mask != 0);
-    }
-    *result_index = plan.passes() & 1;
-    prof_break_chain();  // markers chain only between this run's own passes
-    if (timesteps == 0) return SMI_SUCCESS;
-    int kmax = 0;  // deepest K-step phase (sizes the depth-K staging)
-    for (int i = 0; i < plan.nph; ++i) kmax = std::max(kmax, plan.k[i] >= SWEEPK_MIN ? plan.k[i] : 0);
-
-    // single-step arguments (modes / halo views set below)
-    SweepArgs a{};
-    a.rows = rows;
-    a.cols = cols;
-    for (int k = 0; k < 4; ++k) a.mode[k] = side_nb[k] >= 0 ? SMI_SIDE_HALO : SMI_SIDE_COPY;
-    Sweep2Args a2{};
-    a2.rows = rows;
-    a2.cols = cols;
-    for (int k = 0; k < 4; ++k) a2.skip[k] = side_nb[k] >= 0;
-    // K-step passes: the interior sweep stays K rows / 4*ceil(K/4) columns
-    // clear of every halo-facing side (the band kernel computes those bands
-    // beside it); global edges are handled inside the sweep (stencilk.h).
-    auto interior_args = [&](int K) {
-        SweepKArgs ak{};
-        ak.rows = rows;
-        ak.cols = cols;
-        const int kc = kc_of(K);
-        ak.row_lo = nb.top >= 0 ? K : 0;
-        ak.row_hi = nb.bottom >= 0 ? rows - K : rows;
-        ak.col_lo = nb.left >= 0 ? kc : 0;
-        ak.col_hi = nb.right >= 0 ? cols - kc : cols;
-        ak.gT = nb.top < 0;
-        ak.gB = nb.bottom < 0;
-        ak.gL = nb.left < 0;
-        ak.gR = nb.right < 0;
-        return ak;
-    };
-    auto band_args = [&]() {
-        BandKArgs bk{};
-        bk.rows = rows;
-        bk.cols = cols;
-        for (int k = 0; k < 4; ++k) bk.has[k] = side_nb[k] >= 0;
-        bk.pack = side_mask != 0;
-        return bk;
-    };
-
-    int cur = 0;  // index of the buffer holding the current state
-    auto bufp = [&](int i) { return i ? buf1 : buf0; };
-
-    if (side_mask == 0) {  // single tile: no halos, no exchange, no events
-        for (int ph = 0; ph < plan.nph; ++ph) {
-            const int K = plan.k[ph];
-            SweepKArgs ak = interior_args(K);
-            for (int p = 0; p < plan.n[ph]; ++p, cur ^= 1) {
-                if (K >= SWEEPK_MIN) {
-                    ak.in = bufp(cur);
-                    ak.out = bufp(cur ^ 1);
-                    SMI_TRY(launch_sweepk(K, ak, s));
-                } else if (K == 2) {
-                    a2.in = bufp(cur);
-                    a2.out = bufp(cur ^ 1);
-                    SMI_TRY(launch_sweep2(a2, s));
-                } else {
-                    a.in = bufp(cur);
-                    a.out = bufp(cur ^ 1);
-                    SMI_TRY(launch_sweep_res(a, resid, s));
-                }
-            }
-        }
-        return SMI_SUCCESS;
-    }
-
-    hipEvent_t ev_edge, ev_int, ev_edge_alt, ev_fin;
-    SMI_TRY(comm_event(c, 0, &ev_edge));
-    SMI_TRY(comm_event(c, 1, &ev_int));
-    SMI_TRY(comm_event(c, 2, &ev_edge_alt));
-    SMI_TRY(comm_event(c, 4, &ev_fin));
-    const bool overlap = g_tune.overlap != 0;
-    const hipStream_t user = s;
-    bool own_stream = false;
-    if (overlap) SMI_TRY(interior_stream(c, user, &s, &own_stream));
-
-    // Halo staging.  Depth 2 (its inner row/column doubles as the depth-1
-    // halo): top2 | bot2 | left2 | right2 | corner(4) | send_left2 |
-    // send_right2 | send_corner(4); then depth K (16-byte aligned): top | bot
-    // (K x cols) | left | right | send_left | send_right (rows x KC, [row][k])
-    // | 4 + 4 K x KC corners.  The regions are sized for the deepest phase; a
-    // shallower phase (the remainder pass) lays its depth out densely from
-    // the start of each region.
-    const size_t need2 = (4 * (size_t)cols + 8 * (size_t)rows + 8 + 3) / 4 * 4;
-    const size_t kcmax = kc_of(kmax);
-    const size_t needk = kmax ? 2 * (size_t)kmax * cols + 4 * (size_t)rows * kcmax + 8 * (size_t)kmax * kcmax : 0;
-    SMI_TRY(ensure_halo(c, need2 + needk));
-    Halo2Buf hb;
-    hb.top2 = c->halo;
-    hb.bot2 = hb.top2 + 2 * (size_t)cols;
-    hb.left2 = hb.bot2 + 2 * (size_t)cols;
-    hb.right2 = hb.left2 + 2 * (size_t)rows;
-    hb.corner = hb.right2 + 2 * (size_t)rows;
-    hb.send_left2 = hb.corner + 4;
-    hb.send_right2 = hb.send_left2 + 2 * (size_t)rows;
-    hb.send_corner = hb.send_right2 + 2 * (size_t)rows;
-    const Halo2 h2 = hb.view();
-    auto halok = [&]() {
-        HaloKBuf hk{};
-        float *p = c->halo + need2;
-        hk.top = p;
-        hk.bot = hk.top + (size_t)kmax * cols;
-        hk.left = hk.bot + (size_t)kmax * cols;
-        hk.right = hk.left + (size_t)rows * kcmax;
-        hk.send_left = hk.right + (size_t)rows * kcmax;
-        hk.send_right = hk.send_left + (size_t)rows * kcmax;
-        float *q = hk.send_right + (size_t)rows * kcmax;
-        for (int k = 0; k < 4; ++k) {
-            hk.corner[k] = q + (size_t)k * kmax * kcmax;
-            hk.send_corner[k] = q + (size_t)(4 + k) * kmax * kcmax;
-        }
-        return hk;
-    };
-    // depth-1 views: row -1, row X, col -1, col Y; packed depth-1 sends
-    a.halo[0] = hb.top2 + cols;
-    a.halo[1] = hb.bot2;
-    a.halo[2] = hb.left2 + rows;
-    a.halo[3] = hb.right2;
-    float *s_left = hb.send_left2 + rows;  // depth-1 packed sends (staging only)
-    float *s_right = hb.send_right2;
-    a.send_left = nb.left >= 0 ? s_left : nullptr;
-    a.send_right = nb.right >= 0 ? s_right : nullptr;
-    auto xchg1 = [&](const float *tile, hipStream_t st) {
-        return exchange1(c, nb, tile, rows, cols, const_cast<float *>(a.halo[0]), const_cast<float *>(a.halo[1]),
-                         const_cast<float *>(a.halo[2]), const_cast<float *>(a.halo[3]), s_left, s_right, st);
-    };
-    auto xchg2 = [&](const float *tile, hipStream_t st) { return exchange2(c, nb, tile, rows, cols, hb, st); };
-
-    int kpass = 0;                 // K-step passes of the current phase
-    hipEvent_t last_band = nullptr;  // completion of the phase's last band kernel (host join)
-
-    // Schedule (two streams, no host synchronisation between passes):
-    //   comm stream : [wait interior(t-1)] band(t) -> rec E_edge(t) -> exchange(t)
-    //   main stream : [wait E_edge(t-1)] interior(t)    -> rec E_int(t)
-    // The band kernel (the depth-K bands; the depth-2 / depth-1 phases use
-    // their ring / edge kernels) reads in(t) (interior cells from interior(t-1),
-    // halo-facing cells from its own predecessor) and the halos of
-    // exchange(t-1); the interior reads only in(t), never a halo vector, so
-    // neither the halo-facing cells nor the xGMI exchange sit on its path.
-    // Each phase (K-step passes, the remainder pass, pairs, singles) starts
-    // from halos of the current state: the neighbours' current edges (for
-    // the first phase the reference's artificial timestep t=0,
-    // stencil_smi.cl:26-29,183-224).
-    const bool host_join = overlap && host_join_enabled();
-    auto phase_start = [&]() -> int {
-        SMI_HIP_CHECK(hipEventRecord(ev_int, s));
-        SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
-        return SMI_SUCCESS;
-    };
-    // one pass of a phase: bands (comm stream) + interior (main stream)
-    // ring(st, stop) / interior(st, stop): stop (nullable) = an event the
-    // launch records by its own dispatch (K-step passes: no marker packets
-    // between kernels; ~4 us per pass, tools/streambench); the other phases'
-    // kernels ignore it and it is recorded after them here.
-    auto pass = [&](auto ring, auto interior, auto xchg, bool need_xchg, const float *out, bool carries) -> int {
-        if (overlap && carries && host_join) {
-            // K-step passes, host-observed join (see join_band above):
-            // band(t) carries ev_band[t & 1]; interior(t) follows band(t-1)
-            // with no wait packet when the host has seen band(t-1) finish
-            hipEvent_t ev_cur = (kpass & 1) ? ev_edge_alt : ev_edge, ev_prev = (kpass & 1) ? ev_edge : ev_edge_alt;
-            SMI_TRY(ring(cs, ev_cur));
-            rehearsal_stall(kpass);
-            if (kpass > 0) SMI_TRY(join_band(ev_prev));
-            SMI_TRY(interior(s, ev_int));
-            if (need_xchg) SMI_TRY(xchg(out, cs));
-            SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
-            last_band = ev_cur;
-            ++kpass;
-        } else if (overlap) {
-            // The interior is enqueued before the exchange: posting the
-            // transport's sends/receives costs host time (RCCL group, or
-            // event + copy per message in-process) that must not delay the
-            // interior's launch -- the trace of an interior rank showed the
-            // main stream idle ~100 us per pass behind the exchange calls.
-            SMI_TRY(ring(cs, carries ? ev_edge : nullptr));
-            if (!carries) SMI_HIP_CHECK(hipEventRecord(ev_edge, cs));
-            if (carries) rehearsal_stall(kpass++);
-            SMI_TRY(interior(s, carries ? ev_int : nullptr));
-            if (!carries) SMI_HIP_CHECK(hipEventRecord(ev_int, s));
-            SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_edge, 0));
-            if (need_xchg) SMI_TRY(xchg(out, cs));
-            SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
-        } else {
-            SMI_HIP_CHECK(hipEventRecord(ev_edge, cs));
-            SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_edge, 0));
-            SMI_TRY(ring(s, nullptr));
-            SMI_TRY(interior(s, nullptr));
-            SMI_HIP_CHECK(hipEventRecord(ev_int, s));
-            SMI_HIP_CHECK(hipStreamWaitEvent(cs, ev_int, 0));
-            if (need_xchg) SMI_TRY(xchg(out, cs));
-        }
-        return SMI_SUCCESS;
-    };
-
-    for (int ph = 0; ph < plan.nph; ++ph) {
-        const int K = plan.k[ph], npass = plan.n[ph];
-        SMI_TRY(phase_start());
-        if (K >= SWEEPK_MIN) {
-            // ---- K steps per pass (depth-K halos)
-            const HaloKBuf hk = halok();
-            const HaloK hkv = hk.view();
-            SweepKArgs ak = interior_args(K);
-            BandKArgs bk = band_args();
-            bk.h = hkv;
-            auto xchgk = [&](const float *tile, hipStream_t st) {
-                return exchangek(c, nb, tile, rows, cols, K, hk, st);
-            };
-            SMI_TRY(launch_packk(bufp(cur), rows, cols, K, hkv, cs));
-            SMI_TRY(xchgk(bufp(cur), cs));
-            kpass = 0;
-            for (int p = 0; p < npass; ++p, cur ^= 1) {
-                bk.in = ak.in = bufp(cur);
-                bk.out = ak.out = bufp(cur ^ 1);
-                SMI_TRY(pass([&](hipStream_t st, hipEvent_t stop) {
-                                 return launch_bandk(K, bk, g_tune.band_reserve, st, stop);
-                             },
-                             [&](hipStream_t st, hipEvent_t stop) {
-                                 return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop);
-                             },
-                             xchgk, p < npass - 1, ak.out, true));
-            }
-            // whatever runs next on the main stream reads the last bands:
-            // joined on the host as well (no wait packet on the interior
-            // stream, see join_band)
-            if (host_join && last_band) SMI_TRY(join_band(last_band));
-        } else if (K == 2) {
-            // ---- pairs of steps (depth-2 halos)
-            SMI_TRY(launch_pack2(bufp(cur), rows, cols, h2, cs));
-            SMI_TRY(xchg2(bufp(cur), cs));
-            for (int p = 0; p < npass; ++p, cur ^= 1) {
-                a2.in = bufp(cur);
-                a2.out = bufp(cur ^ 1);
-                SMI_TRY(pass([&](hipStream_t st, hipEvent_t) { return launch_ring2(a2, h2, st); },
-                             [&](hipStream_t st, hipEvent_t) { return launch_sweep2(a2, st); }, xchg2, p < npass - 1,
-                             a2.out, false));
-            }
-        } else {
-            // ---- single steps (depth-1 halos)
-            SMI_TRY(launch_pack_cols(bufp(cur), rows, cols, a.send_left, a.send_right, cs));
-            SMI_TRY(xchg1(bufp(cur), cs));
-            SweepArgs inner = a;  // interior launch: halo-facing sides left to the edge kernel
-            for (int k = 0; k < 4; ++k)
-                if (inner.mode[k] == SMI_SIDE_HALO) inner.mode[k] = SMI_SIDE_SKIP;
-            inner.send_left = inner.send_right = nullptr;
-            for (int t = 0; t < npass; ++t, cur ^= 1) {
-                a.in = inner.in = bufp(cur);
-                a.out = inner.out = bufp(cur ^ 1);
-                if (overlap) {
-                    SMI_TRY(pass([&](hipStream_t st, hipEvent_t) { return launch_edge_res(a, side_mask, resid, st); },
-                                 [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(inner, resid, st); }, xchg1,
-                                 t < npass - 1, a.out, false));
-                } else {
-                    // the full sweep reads the halos itself
-                    SMI_TRY(pass([&](hipStream_t, hipEvent_t) { return (int)SMI_SUCCESS; },
-                                 [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(a, resid, st); }, xchg1,
-                                 t < npass - 1, a.out, false));
-                }
-            }
-        }
-    }
-    // the caller's stream owns the result: join the comm stream (and the
-    // interior stream when the run had one)
-    SMI_HIP_CHECK(hipEventRecord(ev_edge, cs));
-    SMI_HIP_CHECK(hipStreamWaitEvent(user, ev_edge, 0));
-    if (own_stream) {
-        SMI_HIP_CHECK(hipEventRecord(ev_fin, s));
-        SMI_HIP_CHECK(hipStreamWaitEvent(user, ev_fin, 0));
-    }
-    return SMI_SUCCESS;
-}
-
 int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py,
                     int timesteps, SMI_Stream stream_, int *result_index) {
-    Comm *c = lookup_comm(comm);
-    if (!c) {
-        set_error("unknown communicator");
-        return SMI_ERR_BAD_COMM;
-    }
+    Comm *c = nullptr;
+    SMI_TRY(find_comm(comm, &c));
     return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, nullptr);
 }
 
@@ -843,13 +833,9 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
     SMI_ARG_CHECK(max_steps >= 0, "max_steps < 0");
     SMI_ARG_CHECK(check_every >= 1, "check_every must be >= 1");
     SMI_ARG_CHECK(result_index && steps_done && residual, "NULL result_index, steps_done or residual");
-    Comm *c = lookup_comm(comm);
-    if (!c) {
-        set_error("unknown communicator");
-        return SMI_ERR_BAD_COMM;
-    }
-    SMI_TRY(check_tile(buf0, buf1, x_local, y_local));
-    SMI_ARG_CHECK(px >= 1 && py >= 1 && px * py == c->size, "px*py must equal the communicator size");
+    Comm *c = nullptr;
+    SMI_TRY(find_comm(comm, &c));
+    SMI_TRY(check_grid(c, buf0, buf1, x_local, y_local, px, py));
     hipStream_t s = (hipStream_t)stream_;
     if (!c->resid) SMI_HIP_CHECK(hipMalloc(&c->resid, 2 * sizeof(unsigned int)));
     if (!c->resid_host) SMI_HIP_CHECK(hipHostMalloc(&c->resid_host, sizeof(unsigned int), hipHostMallocDefault));

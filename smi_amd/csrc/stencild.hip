@@ -8,27 +8,12 @@ namespace smi {
     int sweepd_launch_k##K(const SweepKArgs &a, const SweepDGeom &g, int blocks, hipStream_t s,          \
                            hipEvent_t start, hipEvent_t stop);                                        \
     int sweepd_resident_k##K();
-SMI_SWEEPD_DECL(13)
-SMI_SWEEPD_DECL(14)
-SMI_SWEEPD_DECL(15)
-SMI_SWEEPD_DECL(16)
-SMI_SWEEPD_DECL(17)
-SMI_SWEEPD_DECL(18)
-SMI_SWEEPD_DECL(19)
-SMI_SWEEPD_DECL(20)
-
-static int resident_waves(int K) {
-    switch (K) {
-    case 13: return sweepd_resident_k13();
-    case 14: return sweepd_resident_k14();
-    case 15: return sweepd_resident_k15();
-    case 16: return sweepd_resident_k16();
-    case 17: return sweepd_resident_k17();
-    case 18: return sweepd_resident_k18();
-    case 19: return sweepd_resident_k19();
-    default: return sweepd_resident_k20();
-    }
-}
+SMI_FOR_K_13_20(SMI_SWEEPD_DECL)
+#define SMI_SWEEPD_ENTRY(K) {sweepd_launch_k##K, sweepd_resident_k##K},
+static constexpr struct {
+    decltype(sweepd_launch_k13) *launch;
+    decltype(sweepd_resident_k13) *resident;
+} kSweepD[] = {SMI_FOR_K_13_20(SMI_SWEEPD_ENTRY)};  // [K - SWEEPD_MIN]
 
 int sweepd_window_cols(int K) { return 256 - 8 * ((K + 3) / 4); }
 
@@ -42,6 +27,7 @@ bool sweepd_fits(int K, const SweepKArgs &a) {
 // blocks shortened by their measured extra cost (g_tune.deep_ce16 /
 // deep_rev16, in 16ths of a block's work).
 int sweepd_geometry(int K, const SweepKArgs &a, int reserve, SweepDGeom *g) {
+    SMI_ARG_CHECK(K >= SWEEPD_MIN && K <= SWEEPD_MAX, "sweepd: steps per pass must be 13..20");
     const int KC = 4 * ((K + 3) / 4), SW = sweepd_window_cols(K);
     const int cs0 = a.col_lo & ~31;
     SweepDGeom r{};
@@ -67,7 +53,7 @@ int sweepd_geometry(int K, const SweepKArgs &a, int reserve, SweepDGeom *g) {
     const int out_rows = a.row_hi - a.row_lo;
     const int ce16 = 16 + std::max(0, g_tune.deep_ce16);
     r.wlast = std::max(4, std::min(16, 256 / (16 + std::max(0, g_tune.deep_rev16))));
-    int waves = g_tune.deep_waves > 0 ? g_tune.deep_waves : resident_waves(K);
+    int waves = g_tune.deep_waves > 0 ? g_tune.deep_waves : kSweepD[K - SWEEPD_MIN].resident();
     SMI_ARG_CHECK(waves > 0, "sweepd: occupancy query failed");
     if (reserve > 0) waves = std::max(64, waves - reserve);
     int nrb = std::max(1, (int)((long)waves * 16 / ((long)r.n_int * 16 + (long)nce * ce16)));
@@ -98,22 +84,10 @@ int sweepd_geometry(int K, const SweepKArgs &a, int reserve, SweepDGeom *g) {
 
 int launch_sweepd(int K, const SweepKArgs &a, int reserve, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     SMI_ARG_CHECK(sweepd_fits(K, a), "sweepd: K out of range or tile too short");
-    SMI_ARG_CHECK(a.cols % 4 == 0 && a.col_lo % 4 == 0 && a.col_hi % 4 == 0, "sweepd: columns not float4 aligned");
-    SMI_ARG_CHECK(a.row_lo >= 0 && a.row_hi <= a.rows && a.col_lo >= 0 && a.col_hi <= a.cols,
-                  "sweepd: output rectangle outside the tile");
+    SMI_TRY(check_sweep_rect("sweepd", a));
     SweepDGeom g;
-    SMI_TRY(sweepd_geometry(K, a, reserve, &g));
-    const int blocks = (g.tasks + 3) / 4;
-    switch (K) {
-    case 13: return sweepd_launch_k13(a, g, blocks, s, start, stop);
-    case 14: return sweepd_launch_k14(a, g, blocks, s, start, stop);
-    case 15: return sweepd_launch_k15(a, g, blocks, s, start, stop);
-    case 16: return sweepd_launch_k16(a, g, blocks, s, start, stop);
-    case 17: return sweepd_launch_k17(a, g, blocks, s, start, stop);
-    case 18: return sweepd_launch_k18(a, g, blocks, s, start, stop);
-    case 19: return sweepd_launch_k19(a, g, blocks, s, start, stop);
-    default: return sweepd_launch_k20(a, g, blocks, s, start, stop);
-    }
+    SMI_TRY(sweepd_geometry(K, a, reserve, &g));  // also refuses a K outside kSweepD
+    return kSweepD[K - SWEEPD_MIN].launch(a, g, (g.tasks + 3) / 4, s, start, stop);
 }
 
 }  // namespace smi
