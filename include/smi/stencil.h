@@ -80,6 +80,35 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local,
                     int y_local, int px, int py, int timesteps,
                     SMI_Stream stream, int *result_index);
 
+/* smi_stencil_run for timesteps >= 1 that also returns the residual of its
+ * final step: the bit pattern of max |x_T - x_{T-1}| over this rank's tile is
+ * max-accumulated into *resid_bits (device memory, 4-byte aligned; the caller
+ * zeroes it; calls may accumulate into one word) -- the contract of
+ * smi_stencil_step_residual (one fp32 subtraction and fabs per cell,
+ * subnormals kept, a NaN if any difference is one, copied global-edge cells
+ * contribute |c - c|), taken inside the last pass of the run: no extra load,
+ * no extra pass, no extra exchange and no host synchronisation beyond the
+ * run's own.  The residual is rank-local: the function does no reduce (a
+ * caller with its own convergence loop reduces the words of its ranks as it
+ * sees fit; smi_stencil_solve does so with smi_reduce + smi_bcast).  The word
+ * is complete when the work enqueued on `stream` has finished.
+ * Schedule (smi_stencil_plan_residual): the last launch is one pass of
+ * K_r = min(steps_per_pass, 12, timesteps) steps, K_r clipped like every
+ * K-step pass of smi_stencil_run on this tile (half the smaller tile side in
+ * a multi-rank run, ...); the timesteps - K_r steps before it are planned
+ * exactly as smi_stencil_run plans that many.  If K_r < 3 (steps_per_pass 1
+ * or 2, fewer than 3 steps, tiles that run single steps only) the last launch
+ * is one single residual step after timesteps - 1 planned steps.  In a
+ * multi-rank run the last pass is an ordinary K_r-step pass (depth-K_r
+ * exchange, band kernel, interior sweep) whose two kernels both post into the
+ * word; every cell of the tile is counted by exactly the kernel that stores it.
+ * The grid is bit-identical to smi_stencil_run(timesteps); *result_index
+ * follows the launch count of this schedule and may differ from
+ * smi_stencil_run's. */
+int smi_stencil_run_residual(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local,
+                             int px, int py, int timesteps, unsigned int *resid_bits,
+                             SMI_Stream stream, int *result_index);
+
 /* Jacobi steps until the residual of a checked step is <= tol, or max_steps.
  * The residual of step t is r_t = max over the global grid of
  * |x_t - x_{t-1}| (the contract of smi_stencil_step_residual: exact, no
@@ -109,6 +138,17 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
                       int px, int py, float tol, int max_steps, int check_every,
                       SMI_Stream stream, int *result_index, int *steps_done,
                       float *residual, int *converged);
+
+/* How smi_stencil_solve takes the residual at a check point.  0 (default): as
+ * described above -- smi_stencil_run for the steps before the check point,
+ * then one single residual step.  1: the steps up to each check point run as
+ * one smi_stencil_run_residual, so the residual comes out of the last K-step
+ * pass and the single step (8 B/cell for one step) is not run at all.
+ * *steps_done, *residual, *converged and the grid are identical for both
+ * settings; only *result_index and the time may differ (DESIGN.md section 7
+ * has the measured cost of a check under both).  fused = -1 keeps the setting. */
+int smi_stencil_set_solve_check(int fused);
+int smi_stencil_get_solve_check(int *fused);
 
 /* Tuning knobs of the sweep kernel (row-block height, rows in flight per
  * wave, non-temporal stores, 1 = overlap halo exchange with the interior).
@@ -206,6 +246,16 @@ typedef struct {
 int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int timesteps,
                      SMI_StencilPhase *phases, int max_phases, int *nphases, int neighbours[8],
                      int *result_index);
+
+/* The schedule smi_stencil_run_residual follows (timesteps >= 1), same
+ * arguments and outputs: the phases smi_stencil_plan gives for the steps
+ * before the final pass, then the final residual pass as a last phase of its
+ * own, (K_r, 1) or (1, 1).  smi_stencil_plan yields at most 3 phases (two
+ * balanced depths, or K-step passes + a pair + a single step), so 4 still
+ * always suffice. */
+int smi_stencil_plan_residual(int x_local, int y_local, int px, int py, int rank, int timesteps,
+                              SMI_StencilPhase *phases, int max_phases, int *nphases,
+                              int neighbours[8], int *result_index);
 
 #ifdef __cplusplus
 }

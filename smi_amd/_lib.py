@@ -98,6 +98,11 @@ SIGNATURES = {
                               ctypes.POINTER(ctypes.c_double)]),
     "smi_prof_list": (I, [ctypes.POINTER(I), ctypes.POINTER(I), I, ctypes.POINTER(I)]),
     "smi_stencil_plan": (I, [I, I, I, I, I, I, P, I, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)]),
+    "smi_stencil_plan_residual": (I, [I, I, I, I, I, I, P, I, ctypes.POINTER(I), ctypes.POINTER(I),
+                                      ctypes.POINTER(I)]),
+    "smi_stencil_run_residual": (I, [SMI_Comm, P, P, I, I, I, I, I, P, P, ctypes.POINTER(I)]),
+    "smi_stencil_set_solve_check": (I, [I]),
+    "smi_stencil_get_solve_check": (I, [ctypes.POINTER(I)]),
 }
 
 

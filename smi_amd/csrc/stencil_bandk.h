@@ -32,6 +32,19 @@
 // microseconds, so a walk that waits on loads row by row is latency-bound),
 // then the walk runs fully unrolled from registers: ~276 cell-levels per lane
 // at K = 12, 4 VALU each (two of them DPP adds), ~800 waves of < 100 VGPRs.
+//
+// Residual instantiations (RES; bandk_res_kernel<K>, K = 3..12, one unit per
+// K in bandk_k<K>_res.hip): the final pass of smi_stencil_run_residual.  When
+// walk() hands a level-K value to `out`, the level-(K-1) value of the same
+// cell is the centre slot of the last ring, and the band arithmetic is exact
+// (x 0.25 every level), so |v_K - v_{K-1}| is one subtraction with nothing to
+// unscale.  Each lane keeps the maximum over the cells it stores -- lanes
+// outside [K, 64 - K) and cells past the band's end hold incomplete cones and
+// are masked out -- over every segment its wave walks; the wave then posts it
+// once (wave_max_u32 + resid_post, as the sweeps do).  Every cell of a tile is
+// stored by exactly one of the interior sweep and this kernel (top / bottom
+// bands: all columns of the K rows; left / right bands: rows [rlo, rhi)), so
+// the two kernels' maxima into one word cover each cell exactly once.
 #pragma once
 
 #include "stencilk.h"
@@ -103,14 +116,16 @@ struct BandW {
     // is the cell at walk position t - l, from level l-1 at inputs t-2,
     // t-1, t (3-slot ring per level, slot = t mod 3, compile-time).  The
     // level-K value of input t (t >= 2K) goes to out(t - 2K, v).  CP: this
-    // lane copies its cell every step (global edge across the walk).
+    // lane copies its cell every step (global edge across the walk).  out
+    // also gets the level-(K-1) value of the same cell (the centre operand
+    // of the last level step), which the residual instantiations use.
     template <bool ROWWALK, bool CP, int N, typename Out>
     __device__ __forceinline__ static void walk(const float (&x)[N], bool cp, Out &&out) {
         float W[K][3];
         static_for<N>([&](auto T) {
             constexpr int t = T;
             W[0][t % 3] = x[t];
-            float v = 0.0f;
+            float v = 0.0f, cK = 0.0f;
             static_for<K>([&](auto L) {
                 constexpr int l = L + 1;
                 if constexpr (t >= 2 * l) {
@@ -118,15 +133,16 @@ struct BandW {
                     v = band_cell<ROWWALK>(W[l - 1][(t + 1) % 3], c, W[l - 1][t % 3]);
                     if constexpr (CP) v = cp ? c : v;
                     if constexpr (l < K) W[l][t % 3] = v;
+                    if constexpr (l == K) cK = c;
                 }
             });
-            if constexpr (t >= 2 * K) out(std::integral_constant<int, t - 2 * K>{}, v);
+            if constexpr (t >= 2 * K) out(std::integral_constant<int, t - 2 * K>{}, v, cK);
         });
     }
 
     // top (BOT = false) or bottom band: lane = column c, rows r0 + t
-    template <bool BOT, bool CP>
-    __device__ __forceinline__ static void rows(const BandKArgs &a, int w, int lane) {
+    template <bool BOT, bool CP, bool RES = false>
+    __device__ __forceinline__ static void rows(const BandKArgs &a, int w, int lane, unsigned int *rmax = nullptr) {
         const int X = a.rows, Y = a.cols;
         const int c = w * SW - K + lane;
         const int r0 = BOT ? X - 2 * K : -K;
@@ -148,9 +164,10 @@ struct BandW {
         const bool store = lane >= K && lane < 64 - K && c < Y;
         const bool cp = (!a.has[2] && c == 0) || (!a.has[3] && c == Y - 1);
         const int KCr = a.kc;
-        walk<true, CP>(x, cp, [&](auto Q, float v) {
+        walk<true, CP>(x, cp, [&](auto Q, float v, float vp) {
             constexpr int q = Q;  // output row r0 + K + q
             if (!store) return;
+            if constexpr (RES) *rmax = max(*rmax, absdiff_bits(v, vp));
             const int r = r0 + K + q;
             a.out[(size_t)r * Y + c] = v;
             if (!a.pack) return;
@@ -167,8 +184,8 @@ struct BandW {
     }
 
     // left (RIGHT = false) or right band: lane = row r, columns c0 + t
-    template <bool RIGHT, bool CP>
-    __device__ __forceinline__ static void cols(const BandKArgs &a, int w, int lane) {
+    template <bool RIGHT, bool CP, bool RES = false>
+    __device__ __forceinline__ static void cols(const BandKArgs &a, int w, int lane, unsigned int *rmax = nullptr) {
         const int X = a.rows, Y = a.cols;
         const int r = a.rlo + w * SW - K + lane;
         // float4 groups [-KC, 2KC) (right: [Y - 2KC, Y + KC)); the walk starts
@@ -189,8 +206,13 @@ struct BandW {
         const bool store = lane >= K && lane < 64 - K && r < a.rhi;
         const bool cp = (!a.has[0] && r == 0) || (!a.has[1] && r == X - 1);
         float o[KC];
-        walk<false, CP>(x, cp, [&](auto Q, float v) { o[Q] = v; });
+        unsigned int m = 0;  // RES: max |v_K - v_{K-1}| over this lane's KC cells
+        walk<false, CP>(x, cp, [&](auto Q, float v, float vp) {
+            o[Q] = v;
+            if constexpr (RES) m = max(m, absdiff_bits(v, vp));
+        });
         if (!store) return;
+        if constexpr (RES) *rmax = max(*rmax, m);
         const int c0 = RIGHT ? Y - KC : 0;
         float *send = RIGHT ? a.h.send_right : a.h.send_left;
         static_for<KC / 4>([&](auto G) {
@@ -212,8 +234,8 @@ struct BandW {
 // Band segment wv: one wave per 64-cell run of a band; segments [first[0],
 // first[1]) top, [first[1], first[2]) bottom, [first[2], first[3]) left,
 // [first[3], first[4]) right.
-template <int K>
-__device__ __forceinline__ void bandk_wave(const BandKArgs &a, int wv, int lane) {
+template <int K, bool RES = false>
+__device__ __forceinline__ void bandk_wave(const BandKArgs &a, int wv, int lane, unsigned int *rmax = nullptr) {
     using B = BandW<K>;
     const int band = (wv >= a.first[1]) + (wv >= a.first[2]) + (wv >= a.first[3]);
     // (no dynamic index into the kernel argument: that would copy it to scratch)
@@ -224,16 +246,16 @@ __device__ __forceinline__ void bandk_wave(const BandKArgs &a, int wv, int lane)
         const int c_lo = w * B::SW - K, c_hi = c_lo + 63;
         const bool cp = (!a.has[2] && c_lo <= 0 && c_hi >= 0) || (!a.has[3] && c_lo <= Y - 1 && c_hi >= Y - 1);
         if (band == 0)
-            cp ? B::template rows<false, true>(a, w, lane) : B::template rows<false, false>(a, w, lane);
+            cp ? B::template rows<false, true, RES>(a, w, lane, rmax) : B::template rows<false, false, RES>(a, w, lane, rmax);
         else
-            cp ? B::template rows<true, true>(a, w, lane) : B::template rows<true, false>(a, w, lane);
+            cp ? B::template rows<true, true, RES>(a, w, lane, rmax) : B::template rows<true, false, RES>(a, w, lane, rmax);
     } else {
         const int r_lo = a.rlo + w * B::SW - K, r_hi = r_lo + 63;
         const bool cp = (!a.has[0] && r_lo <= 0 && r_hi >= 0) || (!a.has[1] && r_lo <= X - 1 && r_hi >= X - 1);
         if (band == 2)
-            cp ? B::template cols<false, true>(a, w, lane) : B::template cols<false, false>(a, w, lane);
+            cp ? B::template cols<false, true, RES>(a, w, lane, rmax) : B::template cols<false, false, RES>(a, w, lane, rmax);
         else
-            cp ? B::template cols<true, true>(a, w, lane) : B::template cols<true, false>(a, w, lane);
+            cp ? B::template cols<true, true, RES>(a, w, lane, rmax) : B::template cols<true, false, RES>(a, w, lane, rmax);
     }
 }
 
@@ -251,6 +273,21 @@ __global__ __launch_bounds__(256) void bandk_kernel(BandKArgs a) {
     const int wv0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     for (int wv = wv0; wv < a.first[4]; wv += waves)  // wave-uniform
         bandk_wave<K>(a, wv, threadIdx.x & 63);
+}
+
+// The residual instantiation: the same segments, the same stores; every wave
+// also posts the maximum of |v_K - v_{K-1}| over the cells it stored.
+template <int K>
+__global__ __launch_bounds__(256) void bandk_res_kernel(BandKArgs a, unsigned int *__restrict__ resid) {
+    const int waves = gridDim.x * 4;
+    const int wv0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    unsigned int rmax = 0;
+    for (int wv = wv0; wv < a.first[4]; wv += waves)  // wave-uniform
+        bandk_wave<K, true>(a, wv, threadIdx.x & 63, &rmax);
+    // all 64 lanes are here again (the loop is wave-uniform, the early returns
+    // inside a segment end at its inlined call): one filtered atomic per wave
+    rmax = wave_max_u32(rmax);
+    if ((threadIdx.x & 63) == 63) resid_post(resid, rmax);
 }
 
 // ---------------------------------------------------------------------------
@@ -589,7 +626,26 @@ int bandk_launch_impl(const BandKArgs &a, int waves, hipStream_t s, hipEvent_t s
     return SMI_SUCCESS;
 }
 
+template <int K>
+int bandk_res_launch_impl(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s, hipEvent_t start,
+                          hipEvent_t stop) {
+    if (start || stop)
+        hipExtLaunchKernelGGL((bandk_res_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, start, stop, 0, a, resid);
+    else
+        hipLaunchKernelGGL((bandk_res_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, a, resid);
+    SMI_HIP_CHECK(hipGetLastError());
+    return SMI_SUCCESS;
+}
+
 }  // namespace smi
+
+#define SMI_BANDK_RES_INSTANCE(K)                                                                        \
+    namespace smi {                                                                                      \
+    int bandk_res_launch_k##K(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s,         \
+                              hipEvent_t start, hipEvent_t stop) {                                       \
+        return bandk_res_launch_impl<K>(a, waves, resid, s, start, stop);                                \
+    }                                                                                                    \
+    }
 
 #define SMI_BANDK_INSTANCE(K)                                                                            \
     namespace smi {                                                                                      \

@@ -20,6 +20,13 @@ SMI_FOR_K_13_20(SMI_BANDL_DECL)
 static constexpr decltype(bandk_launch_k3) *kBandK[] = {SMI_FOR_K_3_12(SMI_BANDK_ENTRY)
                                                         SMI_FOR_K_13_20(SMI_BANDK_ENTRY)};
 static constexpr decltype(bandl_launch_k13) *kBandL[] = {SMI_FOR_K_13_20(SMI_BANDL_ENTRY)};
+// the residual instantiations (bandk_k<K>_res.hip), [K - SWEEPK_MIN]
+#define SMI_BANDK_RES_DECL(K)                                                                    \
+    int bandk_res_launch_k##K(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s, \
+                              hipEvent_t start, hipEvent_t stop);
+SMI_FOR_K_3_12(SMI_BANDK_RES_DECL)
+#define SMI_BANDK_RES_ENTRY(K) bandk_res_launch_k##K,
+static constexpr decltype(bandk_res_launch_k3) *kBandKRes[] = {SMI_FOR_K_3_12(SMI_BANDK_RES_ENTRY)};
 
 static int compute_units() {
     static int cached[64] = {};
@@ -73,7 +80,8 @@ int plan_bands(int K, BandKArgs *ap, bool lean) {
     return SMI_SUCCESS;
 }
 
-int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t stop) {
+int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t stop, unsigned int *resid) {
+    SMI_ARG_CHECK(!resid || K <= SWEEPK_MAX, "bandk: the residual pass runs K <= 12");
     const bool lean = K >= SWEEPD_MIN && g_tune.band_lean;
     SMI_TRY(plan_bands(K, &a, lean));
     const int segs = a.first[4];
@@ -99,6 +107,8 @@ int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t st
         int blocks = std::min(cus, (segs + 3) / 4);
         if (max_waves > 0) blocks = std::min(blocks, std::max(1, max_waves / 4));
         SMI_TRY(kBandL[K - SWEEPD_MIN](a, blocks, s, start, kstop));
+    } else if (resid) {
+        SMI_TRY(kBandKRes[K - SWEEPK_MIN](a, n, resid, s, start, kstop));
     } else {
         SMI_TRY(kBandK[K - SWEEPK_MIN](a, n, s, start, kstop));
     }

@@ -89,6 +89,7 @@ struct Tuning {
     // CU), 0 = one wave per segment (bandk_kernel)
     int band_lean = 1;
     int host_join = 1;  // smi_stencil_set_join
+    int solve_fused = 0;  // smi_stencil_set_solve_check: 1 = smi_stencil_solve checks with a fused K-step pass
 };
 extern Tuning g_tune;
 
@@ -151,7 +152,7 @@ inline int check_sweep_rect(const char *who, const SweepKArgs &a) {
 __host__ __device__ constexpr int sweepk_apron_lanes(int K) { return K >= 9 ? 4 : (K + 3) / 4; }
 int launch_sweepk(int K, const SweepKArgs &a, hipStream_t s);
 int launch_sweepk_ex(int K, const SweepKArgs &a, int ht, int reserve, bool prof, hipStream_t s,
-                     hipEvent_t stop = nullptr);
+                     hipEvent_t stop = nullptr, unsigned int *resid = nullptr);
 int sweepk_window_cols(int K);  // output columns per 256-column window
 
 // Deep K-step sweep (stencild.h / stencild.hip, SWEEPD_MIN <= K <= SWEEPD_MAX):
@@ -220,8 +221,11 @@ struct BandKArgs {
 };
 int plan_bands(int K, BandKArgs *a, bool lean);  // fills kc, first[], sw, rlo, rhi
 // the bands of a pass: one wave per segment, or max_waves (> 0) waves;
-// stop (nullable): an event the launch's dispatch records at completion
-int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t stop = nullptr);
+// stop (nullable): an event the launch's dispatch records at completion;
+// resid (nullable, K <= 12): the residual instantiation, which also
+// max-accumulates |v_K - v_{K-1}| of the band cells into *resid
+int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t stop = nullptr,
+                 unsigned int *resid = nullptr);
 int launch_packk(const float *in, int rows, int cols, int K, const HaloK &h, hipStream_t s);
 
 }  // namespace smi

@@ -133,7 +133,7 @@ struct Tile {
     int rows, cols;
     Neighbours nb;
     int side_mask;        // bit 0..3: neighbour on side top, bottom, left, right
-    unsigned int *resid;  // the checked step of smi_stencil_solve, else nullptr
+    unsigned int *resid;  // the residual word while the final phase of a residual run is enqueued, else nullptr
     int cur;              // index of the buffer holding the current state
     const float *in() const { return buf[cur]; }
     float *out() const { return buf[cur ^ 1]; }
@@ -330,18 +330,20 @@ struct Plan {
     int nph = 0;
     int k[4] = {0, 0, 0, 0};  // steps per pass
     int n[4] = {0, 0, 0, 0};  // passes
+    bool resid_last = false;  // the last phase is the residual pass of smi_stencil_run_residual
     int passes() const { return n[0] + n[1] + n[2] + n[3]; }
+    void add(int steps, int count) {
+        if (count > 0) {
+            k[nph] = steps;
+            n[nph] = count;
+            ++nph;
+        }
+    }
 };
 
-static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
-    Plan p;
-    auto add = [&](int k, int n) {
-        if (n > 0) {
-            p.k[p.nph] = k;
-            p.n[p.nph] = n;
-            ++p.nph;
-        }
-    };
+// The configured steps per pass as far as this tile can hold them (0: no
+// K-step passes), before the deep sweep's own height rule.
+static int tile_fuse(int rows, int cols, bool multi) {
     const int fuse = g_tune.fuse;
     int K = fuse >= SWEEPK_MIN ? fuse : 0;
     if (K && multi) {
@@ -350,6 +352,14 @@ static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
         K = std::min(K, rows / 2);
         while (K > 0 && 8 * ((K + 3) / 4) > cols) --K;
     }
+    return K;
+}
+
+static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
+    Plan p;
+    auto add = [&](int k, int n) { p.add(k, n); };
+    const int fuse = g_tune.fuse;
+    int K = tile_fuse(rows, cols, multi);
     if (K > SWEEPK_MAX) {
         // deep passes (stencild.h) need a tall enough sweep rectangle (a
         // multi-rank interior loses K rows per side with a neighbour; the
@@ -377,6 +387,25 @@ static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
     return p;
 }
 
+// smi_stencil_run_residual: the run ends in ONE pass whose kernels also take
+// |x_T - x_{T-1}|.  That is a pass of K_r = min(steps per pass, 12,
+// timesteps) steps under the tile's clipping rules (the residual lives in the
+// K = 3..12 sweep and the one-wave-per-segment band kernel; the rotating-ring
+// sweep and the lean band kernel have none), after timesteps - K_r steps
+// planned as smi_stencil_run plans them; or, when K_r < 3 (a fusion setting
+// of 1 or 2, fewer than 3 steps, tiles that run single steps only), one
+// single residual step after timesteps - 1 planned steps.  The residual pass
+// is its own last phase; make_plan yields at most 3 phases (two balanced
+// depths, or K + pair + single), so 4 still hold every schedule.
+static Plan make_plan_residual(int rows, int cols, int timesteps, bool multi) {
+    int kr = std::min(std::min(tile_fuse(rows, cols, multi), SWEEPK_MAX), timesteps);
+    if (cols < 8 || kr < SWEEPK_MIN) kr = 1;
+    Plan p = make_plan(rows, cols, timesteps - kr, multi);
+    p.add(kr, 1);
+    p.resid_last = true;
+    return p;
+}
+
 // single-step / pair arguments (halo views and buffers set by the phases)
 static SweepArgs step_args(const Tile &t) {
     SweepArgs a{};
@@ -394,17 +423,18 @@ static Sweep2Args pair_args(const Tile &t) {
 }
 
 // The single-tile run: no halos, no exchange, no events.
-static int run_single(Tile &t, const Plan &plan, hipStream_t s) {
+static int run_single(Tile &t, const Plan &plan, unsigned int *resid, hipStream_t s) {
     SweepArgs a = step_args(t);
     Sweep2Args a2 = pair_args(t);
     for (int ph = 0; ph < plan.nph; ++ph) {
         const int K = plan.k[ph];
+        t.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
         SweepKArgs ak = interior_rect(t.rows, t.cols, K, 0);
         for (int p = 0; p < plan.n[ph]; ++p, t.cur ^= 1) {
             if (K >= SWEEPK_MIN) {
                 ak.in = t.in();
                 ak.out = t.out();
-                SMI_TRY(launch_sweepk(K, ak, s));
+                SMI_TRY(launch_sweepk_ex(K, ak, 0, 0, true, s, nullptr, t.resid));
             } else if (K == 2) {
                 a2.in = t.in();
                 a2.out = t.out();
@@ -514,9 +544,12 @@ static int k_passes(Tile &t, PassSched &sc, int K, int npass, const HaloK &hk) {
     for (int k = 0; k < 4; ++k) bk.has[k] = t.has(k);
     bk.pack = t.side_mask != 0;
     bk.h = hk;
-    auto ring = [&](hipStream_t st, hipEvent_t stop) { return launch_bandk(K, bk, g_tune.band_reserve, st, stop); };
+    // t.resid: the residual pass -- both kernels' residual instantiations, one word
+    auto ring = [&](hipStream_t st, hipEvent_t stop) {
+        return launch_bandk(K, bk, g_tune.band_reserve, st, stop, t.resid);
+    };
     auto interior = [&](hipStream_t st, hipEvent_t stop) {
-        return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop);
+        return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop, t.resid);
     };
     auto xchgk = [&](const float *tile, hipStream_t st) { return exchange(t.c, msgsk(t, tile, K, hk), true, st); };
     SMI_TRY(launch_packk(t.in(), t.rows, t.cols, K, hk, sc.cs));
@@ -590,7 +623,7 @@ static int single_steps(Tile &t, PassSched &sc, int npass, const Halo2 &h2) {
 
 // The multi-rank run: streams and events, the phases, the join back to the
 // caller's stream.
-static int run_multi(Tile &t, const Plan &plan, hipStream_t user) {
+static int run_multi(Tile &t, const Plan &plan, unsigned int *resid, hipStream_t user) {
     Comm *c = t.c;
     PassSched sc{};
     sc.s = user;
@@ -613,6 +646,7 @@ static int run_multi(Tile &t, const Plan &plan, hipStream_t user) {
 
     for (int ph = 0; ph < plan.nph; ++ph) {
         const int K = plan.k[ph], npass = plan.n[ph];
+        t.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
         SMI_TRY(sc.phase_start());
         if (K >= SWEEPK_MIN)
             SMI_TRY(k_passes(t, sc, K, npass, halok_layout(c->halo + need2, t.rows, t.cols, kmax)));
@@ -646,15 +680,17 @@ static int find_comm(SMI_Comm comm, Comm **c) {
     return SMI_ERR_BAD_COMM;
 }
 
-// smi_stencil_run (resid == nullptr), or -- for the checked step of
-// smi_stencil_solve -- the same schedule restricted to single steps whose
-// kernels also max-accumulate |out - in| into *resid (stencil.hip).
+// smi_stencil_run (resid == nullptr), or smi_stencil_run_residual: the
+// schedule of make_plan_residual, whose last pass's kernels also
+// max-accumulate |x_T - x_{T-1}| into *resid (timesteps >= 1; one step is the
+// checked step of smi_stencil_solve: a single residual step, stencil.hip).
 static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local, int px, int py, int timesteps,
                      SMI_Stream stream_, int *result_index, unsigned int *resid) {
     SMI_TRY(check_grid(c, buf0, buf1, x_local, y_local, px, py));
     SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
     SMI_ARG_CHECK(result_index, "NULL result_index");
-    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, resid, 0};
+    SMI_ARG_CHECK(!resid || timesteps >= 1, "a residual run takes at least one step");
+    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, nullptr, 0};
 #ifdef SMI_LOOPBACK_REHEARSAL
     // Timing-rehearsal build only (never the product library; built by
     // `smi_amd/build.py --rehearsal`, driven by tools/rehearsal.py): with
@@ -671,18 +707,13 @@ static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local
     for (int k = 0; k < 4; ++k)
         if (side_nb[k] >= 0) t.side_mask |= 1 << k;
 
-    Plan plan;
-    if (resid) {  // single steps only
-        plan.nph = timesteps > 0;
-        plan.k[0] = 1;
-        plan.n[0] = timesteps;
-    } else {
-        plan = make_plan(t.rows, t.cols, timesteps, t.side_mask != 0);
-    }
+    const bool multi = t.side_mask != 0;
+    const Plan plan = resid ? make_plan_residual(t.rows, t.cols, timesteps, multi)
+                            : make_plan(t.rows, t.cols, timesteps, multi);
     *result_index = plan.passes() & 1;
     prof_break_chain();  // markers chain only between this run's own passes
     if (timesteps == 0) return SMI_SUCCESS;
-    return t.side_mask == 0 ? run_single(t, plan, (hipStream_t)stream_) : run_multi(t, plan, (hipStream_t)stream_);
+    return multi ? run_multi(t, plan, resid, (hipStream_t)stream_) : run_single(t, plan, resid, (hipStream_t)stream_);
 }
 
 
@@ -795,15 +826,16 @@ int smi_stencil_deep_geometry(int rows, int cols, int K, int side_mask, int *wav
     return SMI_SUCCESS;
 }
 
-int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int timesteps, SMI_StencilPhase *phases,
-                     int max_phases, int *nphases, int *neighbours, int *result_index) {
+static int plan_query(bool residual, int x_local, int y_local, int px, int py, int rank, int timesteps,
+                      SMI_StencilPhase *phases, int max_phases, int *nphases, int *neighbours, int *result_index) {
     SMI_ARG_CHECK(x_local >= 1 && y_local >= 4 && y_local % 4 == 0, "tile must be >= 1 x 4, y_local % 4 == 0");
     SMI_ARG_CHECK(px >= 1 && py >= 1 && rank >= 0 && rank < px * py, "rank outside the px x py grid");
-    SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
+    SMI_ARG_CHECK(timesteps >= (residual ? 1 : 0), residual ? "a residual run takes at least one step" : "timesteps < 0");
     SMI_ARG_CHECK(nphases && (phases || max_phases == 0), "NULL output");
     const Neighbours nb = neighbours_of(rank, px, py);
     const bool multi = nb.top >= 0 || nb.bottom >= 0 || nb.left >= 0 || nb.right >= 0;
-    const Plan p = make_plan(x_local, y_local, timesteps, multi);
+    const Plan p = residual ? make_plan_residual(x_local, y_local, timesteps, multi)
+                            : make_plan(x_local, y_local, timesteps, multi);
     SMI_ARG_CHECK(max_phases >= p.nph, "max_phases too small (4 always suffice)");
     for (int i = 0; i < p.nph; ++i) {
         phases[i].steps_per_pass = p.k[i];
@@ -816,6 +848,39 @@ int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int tim
     }
     if (result_index) *result_index = p.passes() & 1;
     return SMI_SUCCESS;
+}
+
+int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int timesteps, SMI_StencilPhase *phases,
+                     int max_phases, int *nphases, int *neighbours, int *result_index) {
+    return plan_query(false, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
+                      result_index);
+}
+
+int smi_stencil_plan_residual(int x_local, int y_local, int px, int py, int rank, int timesteps,
+                              SMI_StencilPhase *phases, int max_phases, int *nphases, int *neighbours,
+                              int *result_index) {
+    return plan_query(true, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
+                      result_index);
+}
+
+int smi_stencil_set_solve_check(int fused) {
+    SMI_ARG_CHECK(fused <= 1, "solve check: 0 (a single residual step) or 1 (a fused K-step residual pass)");
+    if (fused >= 0) g_tune.solve_fused = fused;
+    return SMI_SUCCESS;
+}
+
+int smi_stencil_get_solve_check(int *fused) {
+    if (fused) *fused = g_tune.solve_fused;
+    return SMI_SUCCESS;
+}
+
+int smi_stencil_run_residual(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py,
+                             int timesteps, unsigned int *resid_bits, SMI_Stream stream_, int *result_index) {
+    Comm *c = nullptr;
+    SMI_TRY(find_comm(comm, &c));
+    SMI_ARG_CHECK(timesteps >= 1, "a residual run takes at least one step");
+    SMI_ARG_CHECK(resid_bits && ((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
+    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, resid_bits);
 }
 
 int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py,
@@ -846,14 +911,23 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
     float r = __builtin_inff();
     while (done < max_steps) {
         const int next = (int)std::min((long)done + check_every, (long)max_steps);
-        // the unchecked steps, exactly as smi_stencil_run plans that many
-        SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done - 1, stream_, &idx, nullptr));
-        cur ^= idx;
-        // the checked step; its kernels run on this communicator's streams,
-        // all ordered after `stream` here and joined back to it at the end
-        SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
-        SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, local));
-        cur ^= idx;
+        if (g_tune.solve_fused) {
+            // smi_stencil_set_solve_check(1): the steps up to the check point
+            // as one residual run, whose last K-step pass carries the residual
+            SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
+            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done, stream_, &idx, local));
+            cur ^= idx;
+        } else {
+            // the unchecked steps, exactly as smi_stencil_run plans that many
+            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done - 1, stream_, &idx,
+                              nullptr));
+            cur ^= idx;
+            // the checked step; its kernels run on this communicator's streams,
+            // all ordered after `stream` here and joined back to it at the end
+            SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
+            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, local));
+            cur ^= idx;
+        }
         done = next;
         // the same word on every rank: integer max of the patterns to rank 0
         // and back (the float SMI_MAX starts from FLT_MIN, fold.h, and would

@@ -59,6 +59,34 @@
 // stream in (frexp exponents) and a block that fails walks again with the
 // exact arithmetic.  The multiply was 2 of the 12 VALU instructions of a
 // level step (4 of 16.3 issue-slot units, packed ops at half rate).
+//
+// Residual instantiations (RES; sweepk_res_kernel<K>, one translation unit per
+// K in stencilk_k<K>_res.hip).  When the level-K row of a cell is stored, the
+// level-(K-1) row of the same cell is the centre slot of the last ring, so
+// |x_T - x_{T-1}| of the pass's final step is one subtraction away: same
+// loads, level arithmetic and stores as the plain instantiation, plus a
+// per-lane running maximum of the bit pattern of |v_K - v_{K-1}| (the
+// contract of smi_stencil_step_residual: one fp32 subtraction and fabs,
+// subnormals kept, any NaN wins; a copied global-edge cell contributes
+// |c - c|, which is 0, or NaN for an Inf / NaN cell).
+//   Scaled walk: the ring holds u_K = 4^K v_K and u_{K-1} = 4^(K-1) v_{K-1}.
+// Both are unscaled first, u_K * 4^-K (the store's own product) and
+// u_{K-1} * 4^-(K-1), then subtracted.  Under the wave's guard both products
+// are exact for the same reason the store's is: the scaled levels equal 4^l
+// times the reference's level values EXACTLY (no overflow, every x 0.25 of the
+// reference exact), the reference's v_l is itself an fp32 number (normal or
+// subnormal, a multiple of 2^(-123-2l) >= 2^-149), and a power-of-two product
+// whose exact result is representable is not rounded.  So the two operands of
+// the subtraction are bit for bit the exact walk's, and so is the difference.
+//   A wave whose guard fails walks its block again with the exact arithmetic
+// and discards the scaled walk's maximum: the maximum lives in a register,
+// is reset at the start of every walk and is posted only after a walk that
+// counts -- at most one atomic per wave, behind the filter of the single-step
+// kernels (resid_post).
+//   Lanes and rows that do not store hold values of incomplete cones (apron
+// lanes, rows outside [o0, o1), columns outside [col_lo, col_hi)): the
+// store's hardware range check drops them, a register maximum must mask them
+// out itself (`stl` and the row's in_block below).
 #pragma once
 
 #include <type_traits>
@@ -66,6 +94,7 @@
 #include <hip/hip_ext.h>
 
 #include "stencil_common.h"
+#include "stencil_resid_dev.h"
 
 #ifndef SMI_SWEEPK_SCALED
 #define SMI_SWEEPK_SCALED 1
@@ -134,7 +163,7 @@ enum { ROW_NONE = 0, ROW_TOP = 1, ROW_BOT = 2, ROW_FULL = 3, ROW_UP = 4 };
 // read hits L2.  Needs an even number of row blocks (launch_sweepk_ex).
 __host__ __device__ constexpr bool walks_up(int row) { return row == ROW_BOT || row == ROW_UP; }
 
-template <int K, int U>
+template <int K, int U, bool RES = false>
 struct SweepK {
     static_assert(K >= SWEEPK_MIN && K <= SWEEPK_MAX, "3 <= K <= 12");
     static_assert(U % 3 == 0, "batch must be a multiple of the 3-slot ring");
@@ -144,6 +173,7 @@ struct SweepK {
     static constexpr bool kScaled = SMI_SWEEPK_SCALED != 0;
     static constexpr int kExpLo = -99, kExpHi = 101;      // frexp exponent range of the scaled walk's inputs
     static constexpr float kUnscale = 1.0f / (float)(1u << (2 * K));  // 4^-K (exact: K <= 12)
+    static constexpr float kUnscalePrev = 4.0f * kUnscale;            // 4^-(K-1): level K-1 (RES)
 
     const float *__restrict__ in;
     float *__restrict__ out;
@@ -155,6 +185,11 @@ struct SweepK {
     int row_bytes;
     bool copyL, copyR, gT, gB;
     float4 W[K][3];   // level 0..K-1, slot = input row index mod 3
+    // RES only: the residual word, this lane's running maximum of the walk in
+    // progress, and whether the lane stores (voff in range)
+    unsigned int *resid;
+    unsigned int rmax;
+    bool stl;
 
     template <bool REV>
     __device__ __forceinline__ float4 ld(int t) const {
@@ -249,7 +284,7 @@ struct SweepK {
             v = level<ROW, CE, SC, PH>(l, t, W[l - 1]);
             if constexpr (l < K) W[l][PH] = v;
         });
-        store_row<walks_up(ROW), SC>(t, v);
+        store_row<walks_up(ROW), SC>(t, v, W[K - 1][(PH + 2) % 3]);
     }
 
     // Branch-free predicated store of the level-K row produced by input t:
@@ -258,8 +293,10 @@ struct SweepK {
     // carry an offset beyond it and the hardware range check drops them.  No
     // branch splits the unrolled rows, so the scheduler interleaves their
     // dependency chains.  Nontemporal: the output is not re-read this pass.
+    // cs: the level-(K-1) row of the same cells (the centre slot of the last
+    // ring); RES takes |v - c| of the stored cells from it.
     template <bool REV, bool SC>
-    __device__ __forceinline__ void store_row(int t, const float4 &vs) const {
+    __device__ __forceinline__ void store_row(int t, const float4 &vs, const float4 &cs) {
         float4 v = vs;
         if constexpr (SC) {  // 4^K u -> u: exact (see "Scaled levels")
             const f32x2 q = {kUnscale, kUnscale};
@@ -275,6 +312,18 @@ struct SweepK {
         const u32x4 d = {__builtin_bit_cast(unsigned int, v.x), __builtin_bit_cast(unsigned int, v.y),
                          __builtin_bit_cast(unsigned int, v.z), __builtin_bit_cast(unsigned int, v.w)};
         __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff, 0, 2 /* nt */);
+        if constexpr (RES) {
+            float4 c = cs;
+            if constexpr (SC) {  // 4^(K-1) u -> u: exact (see "Residual instantiations")
+                const f32x2 q = {kUnscalePrev, kUnscalePrev};
+                const f32x2 a = f32x2{cs.x, cs.y} * q, b = f32x2{cs.z, cs.w} * q;
+                c = make_float4(a.x, a.y, b.x, b.y);
+            }
+            const unsigned int m = max(max(absdiff_bits(v.x, c.x), absdiff_bits(v.y, c.y)),
+                                       max(absdiff_bits(v.z, c.z), absdiff_bits(v.w, c.w)));
+            // only the cells the store above really writes
+            rmax = max(rmax, (in_block && stl) ? m : 0u);
+        }
     }
 
     // Walks the block; returns false (wave-uniform) when SC and some input
@@ -285,6 +334,7 @@ struct SweepK {
         constexpr bool REV = walks_up(ROW);
         emin = 0;
         emax = 0;
+        if constexpr (RES) rmax = 0;  // a walk that does not count leaves nothing behind
         // prologue: input rows 0 .. 2K, compile-time indices; level l starts
         // at input 2l (the first row it must produce)
         static_for<PRO>([&](auto T) {
@@ -304,7 +354,7 @@ struct SweepK {
                     if constexpr (l < K) W[l][t % 3] = v;
                 }
             });
-            if constexpr (t == 2 * K) store_row<REV, SC>(t, v);
+            if constexpr (t == 2 * K) store_row<REV, SC>(t, v, W[K - 1][(t + 2) % 3]);
         });
         // steady state: 2U input rows per iteration, loads one batch ahead
         const int n_in = (o1 - o0) + 2 * K;
@@ -351,16 +401,30 @@ struct SweepK {
     template <int ROW, int CE>
     __device__ __forceinline__ void go() {
         if constexpr (kScaled && ROW != ROW_FULL) {
-            if (run<ROW, CE, true>()) return;
+            if (run<ROW, CE, true>()) {
+                post();
+                return;
+            }
         }
         run<ROW, CE, false>();
+        post();
+    }
+
+    // RES: the maximum of the walk that counted, one filtered atomic per wave
+    // (every lane of the wave is here: all control flow above is wave-uniform)
+    __device__ __forceinline__ void post() {
+        if constexpr (RES) {
+            const unsigned int m = wave_max_u32(rmax);
+            if ((threadIdx.x & 63) == 63) resid_post(resid, m);
+        }
     }
 };
 
 // The interior task of one wave: row block rb of strip `strip`.
-template <int K>
-__device__ __forceinline__ void sweepk_task(const SweepKArgs &a, int strip, int rb, int nrb, int lane) {
-    using S = SweepK<K, 3>;
+template <int K, bool RES = false>
+__device__ __forceinline__ void sweepk_task(const SweepKArgs &a, int strip, int rb, int nrb, int lane,
+                                            unsigned int *resid = nullptr) {
+    using S = SweepK<K, 3, RES>;
     constexpr int SW = 256 - 2 * S::KC;  // output columns per window
     S w;
     w.in = a.in;
@@ -380,6 +444,10 @@ __device__ __forceinline__ void sweepk_task(const SweepKArgs &a, int strip, int 
     const bool st = lane >= S::LL && lane < 64 - S::LL && cb >= a.col_lo && cb < a.col_hi;
     w.row_bytes = a.cols * 4;
     w.voff = st ? cb * 4 : 0x7ffffff0;
+    if constexpr (RES) {
+        w.resid = resid;
+        w.stl = st;
+    }
     w.copyL = a.gL && cb == 0;
     w.copyR = a.gR && cb + 4 == a.cols;
     w.gT = a.gT;
@@ -447,6 +515,54 @@ __global__ __launch_bounds__(256) SMI_SWEEPK_WPE_ATTR void sweepk_kernel(SweepKA
     sweepk_task<K>(a, strip, rb, nrb, lane);
 }
 
+// The residual instantiation: the same tasks, each wave also posting the
+// maximum of |v_K - v_{K-1}| over the cells it stores into *resid.
+//   Registers: the residual needs a few more than the plain walk, and at
+// K = 12 (248 VGPRs plain) the allocator would take 264 and drop the kernel to
+// one wave per SIMD; asked for exactly two waves it fits 253 without a spill
+// (asked for "two or more" it spills 12).  Smaller K keep an open upper end.
+#ifdef SMI_SWEEPK_WPE
+#define SMI_SWEEPK_RES_WPE_ATTR SMI_SWEEPK_WPE_ATTR
+#else
+#define SMI_SWEEPK_RES_WPE_ATTR __attribute__((amdgpu_waves_per_eu(2, K >= 12 ? 2 : 8)))
+#endif
+template <int K>
+__global__ __launch_bounds__(256) SMI_SWEEPK_RES_WPE_ATTR void sweepk_res_kernel(SweepKArgs a, int nstrips, int nrb,
+                                                                             unsigned int *__restrict__ resid) {
+    const int lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int lane = threadIdx.x & 63;
+    const int task = __builtin_amdgcn_readfirstlane(lb * 4 + (int)(threadIdx.x >> 6));
+    const int rb = task / nstrips;
+    const int strip = task - rb * nstrips;
+    if (rb >= nrb) return;  // wave-uniform
+    sweepk_task<K, true>(a, strip, rb, nrb, lane, resid);
+}
+
+template <int K>
+int sweepk_res_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, unsigned int *resid, hipStream_t s,
+                           hipEvent_t start, hipEvent_t stop) {
+    if (start || stop)
+        hipExtLaunchKernelGGL((sweepk_res_kernel<K>), dim3(blocks), dim3(256), 0, s, start, stop, 0, a, nstrips, nrb,
+                              resid);
+    else
+        hipLaunchKernelGGL((sweepk_res_kernel<K>), dim3(blocks), dim3(256), 0, s, a, nstrips, nrb, resid);
+    SMI_HIP_CHECK(hipGetLastError());
+    return SMI_SUCCESS;
+}
+
+template <int K>
+int sweepk_res_resident_impl() {
+    static int cached[64] = {};  // per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cached[dev]) return cached[dev];
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweepk_res_kernel<K>, 256, 0) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cached[dev] = per_cu * cus * 4;
+    return cached[dev];
+}
+
 template <int K>
 int sweepk_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, hipStream_t s, hipEvent_t start,
                        hipEvent_t stop) {
@@ -483,4 +599,14 @@ int sweepk_resident_impl() {
         return sweepk_launch_impl<K>(a, nstrips, nrb, blocks, s, start, stop);                           \
     }                                                                                                    \
     int sweepk_resident_k##K() { return sweepk_resident_impl<K>(); }                                     \
+    }
+
+// The residual instantiations, one unit per K as well (stencilk_k<K>_res.hip).
+#define SMI_SWEEPK_RES_INSTANCE(K)                                                                       \
+    namespace smi {                                                                                      \
+    int sweepk_res_launch_k##K(const SweepKArgs &a, int nstrips, int nrb, int blocks, unsigned int *r,   \
+                               hipStream_t s, hipEvent_t start, hipEvent_t stop) {                       \
+        return sweepk_res_launch_impl<K>(a, nstrips, nrb, blocks, r, s, start, stop);                    \
+    }                                                                                                    \
+    int sweepk_res_resident_k##K() { return sweepk_res_resident_impl<K>(); }                             \
     }

@@ -17,6 +17,18 @@ static constexpr struct {
     decltype(sweepk_resident_k3) *resident;
 } kSweepK[] = {SMI_FOR_K_3_12(SMI_SWEEPK_ENTRY)};  // [K - SWEEPK_MIN]; K checked by check_sweepk
 
+// the residual instantiations (stencilk_k<K>_res.hip)
+#define SMI_SWEEPK_RES_DECL(K)                                                                           \
+    int sweepk_res_launch_k##K(const SweepKArgs &a, int nstrips, int nrb, int blocks, unsigned int *r,   \
+                               hipStream_t s, hipEvent_t start, hipEvent_t stop);                        \
+    int sweepk_res_resident_k##K();
+SMI_FOR_K_3_12(SMI_SWEEPK_RES_DECL)
+#define SMI_SWEEPK_RES_ENTRY(K) {sweepk_res_launch_k##K, sweepk_res_resident_k##K},
+static constexpr struct {
+    decltype(sweepk_res_launch_k3) *launch;
+    decltype(sweepk_res_resident_k3) *resident;
+} kSweepKRes[] = {SMI_FOR_K_3_12(SMI_SWEEPK_RES_ENTRY)};
+
 int sweepk_window_cols(int K) { return 256 - 8 * sweepk_apron_lanes(K); }
 
 int launch_sweepk(int K, const SweepKArgs &a, hipStream_t s) { return launch_sweepk_ex(K, a, 0, 0, true, s); }
@@ -25,7 +37,8 @@ int launch_sweepk(int K, const SweepKArgs &a, hipStream_t s) { return launch_swe
 // ht > 0: rows per wave as given; else automatic (g_tune.htk, or one round
 // of resident waves -- minus `reserve` waves left to the comm stream's
 // kernels in a multi-rank run, smi_stencil_set_bands).
-static void sweepk_geometry(int K, const SweepKArgs &a, int ht_req, int reserve, int *nstrips_, int *nrb_) {
+static void sweepk_geometry(int K, const SweepKArgs &a, int ht_req, int reserve, bool res, int *nstrips_,
+                            int *nrb_) {
     const int sw = sweepk_window_cols(K);
     const int nstrips = (a.col_hi - (a.col_lo & ~31) + sw - 1) / sw;  // line-aligned strips (stencilk.h)
     const int out_rows = a.row_hi - a.row_lo;
@@ -36,7 +49,7 @@ static void sweepk_geometry(int K, const SweepKArgs &a, int ht_req, int reserve,
         // comm stream's kernels (one round of the rest), or cut the interior
         // into several rounds so that workgroups retire during the pass and
         // the comm stream's kernels are dispatched then.
-        int waves = kSweepK[K - SWEEPK_MIN].resident();
+        int waves = res ? kSweepKRes[K - SWEEPK_MIN].resident() : kSweepK[K - SWEEPK_MIN].resident();
         const bool single = a.gT && a.gB && a.gL && a.gR;
         int rounds = single ? 1 : std::max(1, g_tune.rounds_multi);
         if (!single && reserve > 0) {
@@ -57,9 +70,11 @@ static int check_sweepk(int K, const SweepKArgs &a) {
 
 // prof: record the launch under SMI_PROF_STENCIL_SWEEPK.  stop (nullable):
 // an event the launch's dispatch records when the kernel completes (or an
-// ordinary record when there is nothing to launch).
+// ordinary record when there is nothing to launch).  resid (nullable): run
+// the residual instantiation, which also max-accumulates |v_K - v_{K-1}| of
+// the cells it stores into *resid (K <= 12 only).
 int launch_sweepk_ex(int K, const SweepKArgs &a, int ht_req, int reserve, bool prof, hipStream_t s,
-                     hipEvent_t stop) {
+                     hipEvent_t stop, unsigned int *resid) {
     if (a.row_hi <= a.row_lo || a.col_hi <= a.col_lo) {
         if (stop) SMI_HIP_CHECK(hipEventRecord(stop, s));
         return SMI_SUCCESS;
@@ -68,12 +83,13 @@ int launch_sweepk_ex(int K, const SweepKArgs &a, int ht_req, int reserve, bool p
     // no row-block override, and wave slots reserved for the band kernel
     // (smi_stencil_set_bands) come off its one round of waves
     const bool deep = K > SWEEPK_MAX;
+    SMI_ARG_CHECK(!(deep && resid), "sweepk: the residual pass runs K <= 12");
     int nstrips = 0, nrb = 0;
     if (deep) {
         SMI_ARG_CHECK(ht_req <= 0, "sweepk: K > 12 has no row-block override");
     } else {
         SMI_TRY(check_sweepk(K, a));
-        sweepk_geometry(K, a, ht_req, reserve, &nstrips, &nrb);
+        sweepk_geometry(K, a, ht_req, reserve, resid != nullptr, &nstrips, &nrb);
     }
     // Timing (profiling on).  Back-to-back single-tile passes: one chained
     // marker per pass (the end marker of pass i is the begin of pass i+1):
@@ -100,7 +116,10 @@ int launch_sweepk_ex(int K, const SweepKArgs &a, int ht_req, int reserve, bool p
         SMI_TRY(launch_sweepd(K, a, reserve, s, start, kstop));
     } else {
         const int blocks = (int)(((long)nstrips * nrb + 3) / 4);
-        SMI_TRY(kSweepK[K - SWEEPK_MIN].launch(a, nstrips, nrb, blocks, s, start, kstop));
+        if (resid)
+            SMI_TRY(kSweepKRes[K - SWEEPK_MIN].launch(a, nstrips, nrb, blocks, resid, s, start, kstop));
+        else
+            SMI_TRY(kSweepK[K - SWEEPK_MIN].launch(a, nstrips, nrb, blocks, s, start, kstop));
     }
     if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
     if (marker) SMI_TRY(prof_end(tok, s));

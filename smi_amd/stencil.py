@@ -105,16 +105,26 @@ def solve(comm: Comm, tile: torch.Tensor, tol: float, max_steps: int, check_ever
 
 
 def run(comm: Comm, tile: torch.Tensor, timesteps: int, PX: int, PY: int,
-        scratch: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        scratch: torch.Tensor | None = None, stream=None, residual: torch.Tensor | None = None) -> torch.Tensor:
     """The whole stencil_smi run on this rank's tile (smi_stencil_run):
     returns the tensor (tile or scratch) holding the result, like the
-    reference's copy-back of half timesteps%2 (stencil_smi.cpp:344)."""
+    reference's copy-back of half timesteps%2 (stencil_smi.cpp:344).
+    residual: a one-element int32 device tensor (zeroed by the caller) that
+    the run's last pass max-accumulates the bit pattern of this rank's
+    max |x_T - x_{T-1}| into (smi_stencil_run_residual, timesteps >= 1;
+    rank-local, no reduce; residual_value() decodes it)."""
     if scratch is None:
         scratch = torch.empty_like(tile)
     X, Y = tile.shape
     idx = ctypes.c_int()
-    _lib.call("smi_stencil_run", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
-              timesteps, _lib.stream_handle(stream, tile.get_device()), ctypes.byref(idx))
+    if residual is None:
+        _lib.call("smi_stencil_run", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
+                  timesteps, _lib.stream_handle(stream, tile.get_device()), ctypes.byref(idx))
+    else:
+        if residual.dtype != torch.int32 or residual.numel() != 1 or not residual.is_cuda:
+            raise ValueError("residual must be a one-element int32 device tensor")
+        _lib.call("smi_stencil_run_residual", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
+                  timesteps, residual.data_ptr(), _lib.stream_handle(stream, tile.get_device()), ctypes.byref(idx))
     return tile if idx.value == 0 else scratch
 
 
@@ -122,16 +132,18 @@ class _Phase(ctypes.Structure):
     _fields_ = [("steps_per_pass", ctypes.c_int), ("passes", ctypes.c_int)]
 
 
-def plan(x_local: int, y_local: int, PX: int, PY: int, rank: int, timesteps: int) -> dict:
+def plan(x_local: int, y_local: int, PX: int, PY: int, rank: int, timesteps: int, residual: bool = False) -> dict:
     """The schedule smi_stencil_run follows on `rank` (host only, no GPU):
     phases [(steps_per_pass, passes), ...], the neighbour ranks (top, bottom,
     left, right, tl, tr, bl, br; -1 on the global edge) and the index of the
-    buffer that ends up holding the result."""
+    buffer that ends up holding the result.  residual=True: the schedule of
+    run(..., residual=word) instead (smi_stencil_plan_residual), whose last
+    phase is the one pass that carries the residual."""
     ph = (_Phase * 4)()
     n = ctypes.c_int()
     nb = (ctypes.c_int * 8)()
     ri = ctypes.c_int()
-    _lib.call("smi_stencil_plan", x_local, y_local, PX, PY, rank, timesteps, ph, 4, ctypes.byref(n), nb,
+    _lib.call("smi_stencil_plan_residual" if residual else "smi_stencil_plan", x_local, y_local, PX, PY, rank, timesteps, ph, 4, ctypes.byref(n), nb,
               ctypes.byref(ri))
     return {"phases": [(ph[i].steps_per_pass, ph[i].passes) for i in range(n.value)],
             "neighbours": list(nb), "result_index": ri.value}
@@ -199,6 +211,20 @@ def set_join(host_join: int = -1) -> None:
 def get_join() -> int:
     v = ctypes.c_int()
     _lib.call("smi_stencil_get_join", ctypes.byref(v))
+    return v.value
+
+
+def set_solve_check(fused: int = -1) -> None:
+    """How solve() takes the residual at a check point (same steps, residual
+    and grid either way): 0 = one single residual step after the run
+    (default), 1 = the last K-step pass of the run carries it
+    (smi_stencil_run_residual).  -1 keeps it (smi_stencil_set_solve_check)."""
+    _lib.call("smi_stencil_set_solve_check", fused)
+
+
+def get_solve_check() -> int:
+    v = ctypes.c_int()
+    _lib.call("smi_stencil_get_solve_check", ctypes.byref(v))
     return v.value
 
 

@@ -19,6 +19,17 @@ Two measurements at 8192^2 on one GPU, appended as JSON lines to --out:
                 (the single residual step, reduce, bcast, 4 bytes back and the
                 host synchronise) = (solve - run) / checks.
 
+  --mode fused  the fused check (smi_stencil_run_residual,
+                smi_stencil_set_solve_check), everything alternating inside one
+                process: (a) one K = 12 pass with and without the residual
+                (sweepk_res_kernel<12> against sweepk_kernel<12>), device events
+                around windows of --passes single-pass runs; (b)
+                smi_stencil_run(T) against smi_stencil_run_residual(T) at T =
+                20 and 100 under the default fusion, device events around
+                windows of --runs runs; (c) solve against run as in --mode
+                solve, with the solve check 0 and 1 alternating, so both
+                per-check costs come from one session.
+
 Not part of bench.py; a GPU is required.
 """
 from __future__ import annotations
@@ -151,18 +162,116 @@ def mode_solve(args) -> None:
     comm.finalize()
 
 
+def mode_fused(args) -> None:
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_solve needs a GPU")
+    import smi_amd
+    from smi_amd import stencil
+    N, T = args.size, args.total_steps
+    comm = smi_amd.LocalGroup(1).comm(0)
+    torch.manual_seed(0)
+    src = torch.rand((N, N), device="cuda")
+    tile, scratch = torch.empty_like(src), torch.empty_like(src)
+    tile.copy_(src)
+    word = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fuse0 = stencil.get_fusion()["steps_per_pass"]
+
+    def window(fn, n) -> float:
+        """ms per call over n back-to-back calls (device events); the buffers ping-pong"""
+        a, b = tile, scratch
+        ev0.record()
+        for _ in range(n):
+            res = fn(a, b)
+            if res is b:
+                a, b = b, a
+        ev1.record()
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) / n
+
+    def timed_pair(kind, steps, n, extra):
+        def plain(a, b):
+            return stencil.run(comm, a, steps, 1, 1, scratch=b)
+
+        def resid(a, b):
+            return stencil.run(comm, a, steps, 1, 1, scratch=b, residual=word)
+
+        variants = [("run", plain), ("run_residual", resid)]
+        times = {name: [] for name, _ in variants}
+        for name, fn in variants:
+            window(fn, n)
+        for _ in range(args.reps):
+            for name, fn in variants:
+                times[name].append(window(fn, n))
+        for name, _ in variants:
+            emit(args.out, dict(kind=kind, label=args.label, variant=name, size=N, steps=steps, calls_per_window=n,
+                                plan=stencil.plan(N, N, 1, 1, 0, steps, residual=name == "run_residual")["phases"],
+                                unit="ms per call", **extra, **summary(times[name])))
+
+    # (a) one K = 12 pass, residual instantiation against plain
+    stencil.set_fusion(steps_per_pass=12)
+    timed_pair("pass_k12", 12, args.passes, dict(steps_per_pass=12))
+    # (b) whole runs under the default fusion
+    stencil.set_fusion(steps_per_pass=fuse0)
+    for steps in (20, 100):
+        timed_pair("run_vs_run_residual", steps, args.runs, dict(steps_per_pass=fuse0))
+
+    # (c) solve / run with both checks
+    def run_once(fn) -> float:
+        tile.copy_(src)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def do_run():
+        stencil.run(comm, tile, T, 1, 1, scratch=scratch)
+
+    check0 = stencil.get_solve_check()
+    for ce in (20, 100, 400):
+        def do_solve(fused):
+            stencil.set_solve_check(fused)
+            _, steps, r, conv = stencil.solve(comm, tile, 0.0, T, ce, 1, 1, scratch=scratch)
+            assert steps == T and not conv, (steps, r, conv)
+
+        fns = [("run", do_run), ("solve_check0", lambda: do_solve(0)), ("solve_check1", lambda: do_solve(1))]
+        for _, fn in fns:
+            run_once(fn)
+        t = {name: [] for name, _ in fns}
+        for _ in range(args.reps):      # alternating
+            for name, fn in fns:
+                t[name].append(run_once(fn))
+        checks = (T + ce - 1) // ce
+        sm = {name: summary(v) for name, v in t.items()}
+        per_check = {name: [(s - r) / checks for s, r in zip(t[name], t["run"])] for name in ("solve_check0",
+                                                                                              "solve_check1")}
+        emit(args.out, dict(kind="solve_vs_run_checks", label=args.label, size=N, steps=T, check_every=ce,
+                            checks=checks, run_ms_per_step=sm["run"]["median_ms"] / T,
+                            solve0_ms_per_step=sm["solve_check0"]["median_ms"] / T,
+                            solve1_ms_per_step=sm["solve_check1"]["median_ms"] / T,
+                            per_check_ms_check0=summary(per_check["solve_check0"]),
+                            per_check_ms_check1=summary(per_check["solve_check1"]),
+                            run=sm["run"], solve_check0=sm["solve_check0"], solve_check1=sm["solve_check1"]))
+    stencil.set_solve_check(check0)
+    comm.finalize()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--mode", choices=("step", "solve"), required=True)
+    ap.add_argument("--mode", choices=("step", "solve", "fused"), required=True)
     ap.add_argument("--lib", default=None, help="step mode: the libsmi_amd.so to time (default: this tree's)")
     ap.add_argument("--label", default="current", help="recorded with every line (e.g. parent / current)")
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--steps", type=int, default=200, help="step mode: single steps per timed window")
     ap.add_argument("--total-steps", type=int, default=2000, help="solve mode: steps of every run / solve")
+    ap.add_argument("--passes", type=int, default=100, help="fused mode: K = 12 passes per timed window")
+    ap.add_argument("--runs", type=int, default=20, help="fused mode: runs per timed window")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solve", "solve.jsonl"))
     args = ap.parse_args()
-    (mode_step if args.mode == "step" else mode_solve)(args)
+    {"step": mode_step, "solve": mode_solve, "fused": mode_fused}[args.mode](args)
 
 
 if __name__ == "__main__":
