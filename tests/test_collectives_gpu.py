@@ -47,6 +47,65 @@ def test_fold_signed_zero_and_nan(gpu, oracle_mod):
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), op
 
 
+def _fold_bytes(c, op):
+    from smi_amd import collectives
+    return collectives.reduce_fold(torch.from_numpy(c).cuda(), op).cpu().numpy().view(np.uint8)
+
+
+@pytest.mark.parametrize("t", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("op", [0, 1, 2])
+@pytest.mark.parametrize("n", [9, 15, 16, 17, 33, 64])
+def test_fold_kernel_many_contributions(gpu, oracle_mod, t, op, n):
+    """More than one batch of 8 rows: the slot state carried from batch to
+    batch, partial last batches (9, 15, 17, 33) and whole ones (16, 64, the
+    ABI's limit).  For float and double a block of columns is also made
+    negative on every row: MAX then returns its FLT_MIN / DBL_MIN start."""
+    for count in (1, 7, 33, 300):
+        c = _contribs(oracle_mod, n, count, t, seed=count * 7 + n)
+        want = oracle_mod.reduce(c, t, op)
+        assert np.array_equal(_fold_bytes(c, op), want.view(np.uint8)), (t, op, n, count)
+        if t in (2, 3):
+            blk = slice(count // 3, count // 3 + (count + 2) // 3)
+            c[:, blk] = -np.abs(c[:, blk]) - 1
+            want = oracle_mod.reduce(c, t, op)
+            if op == 1:
+                assert (want[blk] == np.finfo(c.dtype).tiny).all()
+            assert np.array_equal(_fold_bytes(c, op), want.view(np.uint8)), (t, op, n, count, "negative block")
+
+
+@pytest.mark.parametrize("t", [2, 3, 4])
+@pytest.mark.parametrize("n", [9, 17])
+def test_fold_padded_and_misaligned_rows(gpu, oracle_mod, t, n):
+    """Column windows of a wider tensor (ld > count).  `pad` keeps every row
+    of the parent 16-byte aligned, so t[:, :count] takes the vector path with
+    a scalar tail and t[:, 1:count+1], every row misaligned, the scalar path."""
+    from smi_amd import collectives
+    count = 4099
+    esz = np.dtype(oracle_mod.NP_DTYPE[t]).itemsize
+    pad = next(p for p in range(1, 17) if (count + p) * esz % 16 == 0)
+    w = _contribs(oracle_mod, n, count + pad, t, seed=n + t)
+    dw = torch.from_numpy(w).cuda()
+    assert dw.data_ptr() % 16 == 0 and dw.stride(0) * esz % 16 == 0
+    for op in (0, 1, 2):
+        for lo in (0, 1):
+            view = dw[:, lo:lo + count]
+            assert view.stride(0) == count + pad and (view.data_ptr() % 16 == 0) == (lo == 0)
+            got = collectives.reduce_fold(view, op).cpu().numpy()
+            want = oracle_mod.reduce(np.ascontiguousarray(w[:, lo:lo + count]), t, op)
+            assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (t, n, op, lo)
+
+
+def test_fold_rejects_65_rows_and_ignores_empty_rows(gpu):
+    from smi_amd import SMIError, collectives
+    with pytest.raises(SMIError):
+        collectives.reduce_fold(torch.zeros((65, 8), device="cuda"), "add")
+    out = torch.full((16,), 7.0, device="cuda")
+    wide = torch.ones((9, 16), device="cuda")
+    collectives.reduce_fold(wide[:, :0], "add", out=out)  # count = 0
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == 7.0).all()
+
+
 def _group_reduce(n, sends, t, op, root):
     from smi_amd import LocalGroup, collectives
 

@@ -86,6 +86,87 @@ def test_accumulate_long_chain(gpu, oracle_mod):
     assert np.array_equal(s.cpu().numpy().view(np.uint32), want_s.view(np.uint32))
 
 
+# The fold walks a cluster in LDS tiles of 2048 rows, two steps (register
+# buffers) per loop trip: one row short of a tile, a full tile with no tail, a
+# second tile of one row, two full tiles, a third tile (odd step) of one row,
+# an empty cluster, a single row, three full tiles.
+TILE_EDGE_SIZES = [2047, 2048, 2049, 4096, 4097, 0, 1, 6144]
+
+
+@pytest.mark.parametrize("dims", [12, 8, 1])
+def test_accumulate_tile_boundaries(gpu, oracle_mod, dims):
+    """dims = 12: a full and a partial 8-dimension workgroup; 1: one lane column."""
+    from smi_amd import kmeans
+    asg = np.repeat(np.arange(len(TILE_EDGE_SIZES), dtype=np.int32), TILE_EDGE_SIZES)
+    rng = np.random.default_rng(2048)
+    rng.shuffle(asg)  # every cluster's rows scattered over the points
+    n = len(asg)
+    assert n == 20482
+    pts = rng.standard_normal((n, dims), dtype=np.float32) * 3
+    want_s, want_c = oracle_mod.kmeans_accumulate(pts, asg, len(TILE_EDGE_SIZES))
+    assert want_c.tolist() == TILE_EDGE_SIZES
+    s, c = kmeans.accumulate(dev(pts), dev(asg), len(TILE_EDGE_SIZES))
+    assert np.array_equal(c.cpu().numpy(), want_c)
+    assert np.array_equal(s.cpu().numpy().view(np.uint32), want_s.view(np.uint32))
+
+
+SPECIAL_SEED = 11  # the oracle-side conditions below hold for this seed
+
+
+def special_accumulate_case():
+    """5000 normally distributed points in 4 clusters: cluster 0 starts (in
+    point order) with an all -0.0 point; cluster 1 has one +Inf (dim 2) and one
+    NaN (dim 9); cluster 2 one -Inf (dim 5) and, in dim 11, +Inf before -Inf;
+    cluster 3 is scaled into the subnormal range."""
+    rng = np.random.default_rng(SPECIAL_SEED)
+    n, dims, clusters = 5000, 16, 4
+    pts = rng.standard_normal((n, dims), dtype=np.float32)
+    asg = rng.integers(0, clusters, n).astype(np.int32)
+    members = [np.flatnonzero(asg == k) for k in range(clusters)]
+    pts[members[0][0], :] = -0.0
+    pts[members[1][40], 2] = np.inf
+    pts[members[1][300], 9] = np.nan
+    pts[members[2][17], 5] = -np.inf
+    pts[members[2][100], 11] = np.inf
+    pts[members[2][900], 11] = -np.inf
+    pts[members[3]] = (pts[members[3]].astype(np.float64) * 1e-39).astype(np.float32)
+    return pts, asg, clusters
+
+
+def test_accumulate_special_values(gpu, oracle_mod):
+    """Skipping the other clusters' +0 must not show with -0, Inf, NaN or
+    subnormal coordinates: the literal form of the oracle, NaN-aware bitwise."""
+    from smi_amd import kmeans
+    pts, asg, clusters = special_accumulate_case()
+    want_s, want_c = oracle_mod.kmeans_accumulate(pts, asg, clusters)
+    # the case is what it claims to be, on the oracle alone
+    assert np.isnan(want_s).sum() == 2 and np.isnan(want_s).sum() < want_s.size // 4
+    assert np.isnan(want_s[1, 9]) and np.isnan(want_s[2, 11])
+    assert want_s[1, 2] == np.inf and want_s[2, 5] == -np.inf
+    tiny = np.finfo(np.float32).tiny
+    assert (want_s[3] != 0).all()
+    assert (np.abs(pts[asg == 3]) < tiny).all() and (pts[asg == 3] != 0).mean() > 0.99
+    s, c = kmeans.accumulate(dev(pts), dev(asg), clusters)
+    assert np.array_equal(c.cpu().numpy(), want_c)
+    assert same_bits(s.cpu().numpy(), want_s)
+
+
+def test_assign_at_the_lds_limit(gpu, oracle_mod):
+    """clusters * dims / width = 16384: 64 KiB of dynamic LDS, the documented
+    limit; one more lane per cluster is refused."""
+    from smi_amd import SMIError, kmeans
+    n, dims, clusters = 300, 64, 256
+    rng = np.random.default_rng(16384)
+    pts = rng.standard_normal((n, dims), dtype=np.float32)
+    cen = rng.standard_normal((clusters, dims), dtype=np.float32)
+    want = oracle_mod.kmeans_assign(pts, cen, 1)
+    assert len(np.unique(want)) > 64
+    got = kmeans.assign(dev(pts), dev(cen), 1).cpu().numpy()
+    assert np.array_equal(got, want)
+    with pytest.raises(SMIError):
+        kmeans.assign(torch.zeros((n, 65), device="cuda"), torch.zeros((clusters, 65), device="cuda"), 1)
+
+
 def _run_program(pts, cen0, iters, ranks, width):
     from smi_amd import LocalGroup, kmeans
 

@@ -84,6 +84,27 @@ def test_reduce_c_matches_python_loop(t, op):
         assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
 
 
+@pytest.mark.parametrize("n", [9, 16, 17, 63, 64])
+@pytest.mark.parametrize("t,op", [(2, 0), (2, 1), (1, 0)])
+def test_reduce_c_matches_python_loop_many_ranks(t, op, n):
+    """9 to 64 contributions (the regime of the GPU fold's second and later
+    batches of 8 rows), rank order: float add, float max (with an
+    all-negative column: FLT_MIN comes back), int add (wrapping)."""
+    rng = np.random.default_rng(n * 5 + t + op)
+    npdt = o.NP_DTYPE[t]
+    if t == 2:
+        c = ((rng.random((n, 24)) * 2 - 1) * 1000).astype(npdt)
+        c[:, 3] = -np.abs(c[:, 3]) - 1
+    else:
+        info = np.iinfo(npdt)
+        c = rng.integers(info.min, info.max, size=(n, 24), endpoint=True, dtype=npdt)
+    got = o.reduce(c, t, op)
+    want = np.array([o.reduce_fold_py(c[:, j], t, op) for j in range(c.shape[1])], dtype=npdt)
+    assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
+    if (t, op) == (2, 1):
+        assert got[3] == np.finfo(np.float32).tiny
+
+
 def test_reduce_float_max_init_quirk():
     """codegen/ops.py:133 initialises float MAX with FLT_MIN (smallest
     positive normal), so an all-negative max returns FLT_MIN."""
