@@ -139,6 +139,58 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
                       SMI_Stream stream, int *result_index, int *steps_done,
                       float *residual, int *converged);
 
+/* ---- Jacobi with a source term: -laplace(u) = f, with g = h^2 f ------------
+ * Arithmetic contract (bit-exact):
+ *   interior cell:     out = 0.25f * ((((S + W) + E) + N) + g)
+ *   global-edge cell:  out = in        (g is ignored there)
+ * S, W, E, N as above, g the cell of the caller's array `src`; IEEE fp32 round
+ * to nearest, no contraction, subnormals kept; g is added last, after N and
+ * before the multiply.  `src` has the tile's shape and layout (x_local x
+ * y_local fp32, dense, row-major, 16-byte aligned), overlaps neither buffer
+ * and is never written.  Its cells on the global edge may be read but never
+ * reach a result: a NaN there does not leak.  The residual contract is that of
+ * smi_stencil_step_residual, unchanged.
+ *   g = -0.0f everywhere makes the update bit-identical to the plain one for
+ * every input, because x + (-0) = x, including x = -0.  g = +0.0f does not,
+ * because -0 + +0 = +0: cells whose four-neighbour sum is -0 come out +0.
+ * A NULL, misaligned or overlapping `src` is an argument error like a bad
+ * buf0 / buf1, refused before any device call. */
+
+/* smi_stencil_step with the source term (all three side modes, send_left /
+ * send_right); resid_bits nullable: non-NULL also takes the residual as
+ * smi_stencil_step_residual does.  One more 16-byte load of `src` per four
+ * cells and one more add per cell: 12 B/cell where the plain step moves 8. */
+int smi_stencil_step_source(const float *in, float *out, const float *src, int x_local, int y_local,
+                            const int mode[4], const float *const halo[4], float *send_left,
+                            float *send_right, unsigned int *resid_bits /* nullable */, SMI_Stream stream);
+
+/* smi_stencil_run with the source term; each rank passes its own tile of
+ * `src`.  Schedule (smi_stencil_plan_source).  One tile with y_local >= 8:
+ * fused passes of min(steps_per_pass, KS) steps, KS =
+ * smi_stencil_source_max_depth, with the balanced-remainder rule of
+ * smi_stencil_run (a remainder >= 3 is spread over the passes); a remainder of
+ * 1 or 2 runs as single steps (no pairs), and steps_per_pass < 3 runs single
+ * steps only.  Multi-rank: single steps only, through the depth-1 exchange of
+ * smi_stencil_run -- no multi-rank source pass is fused (there is no band,
+ * ring or pair kernel with a source).  A fused source pass moves 12 B/cell per
+ * up to KS steps and runs the exact arithmetic at every level. */
+int smi_stencil_run_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local,
+                           int y_local, int px, int py, int timesteps, SMI_Stream stream, int *result_index);
+
+/* The loop of smi_stencil_solve with the source term: source runs between the
+ * check points and one single source residual step at each, the same
+ * integer-max reduce and bcast (the fused source pass has no residual variant,
+ * and smi_stencil_set_solve_check does not affect this function). */
+int smi_stencil_solve_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local,
+                             int y_local, int px, int py, float tol, int max_steps, int check_every,
+                             SMI_Stream stream, int *result_index, int *steps_done, float *residual,
+                             int *converged);
+
+/* The deepest fused source pass, KS (6..12): the largest K whose sweep keeps
+ * its level rings and the K live rows of g in registers at two waves per SIMD
+ * without scratch.  Host only. */
+int smi_stencil_source_max_depth(int *k);
+
 /* How smi_stencil_solve takes the residual at a check point.  0 (default): as
  * described above -- smi_stencil_run for the steps before the check point,
  * then one single residual step.  1: the steps up to each check point run as
@@ -256,6 +308,12 @@ int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int tim
 int smi_stencil_plan_residual(int x_local, int y_local, int px, int py, int rank, int timesteps,
                               SMI_StencilPhase *phases, int max_phases, int *nphases,
                               int neighbours[8], int *result_index);
+
+/* The schedule smi_stencil_run_source follows, same arguments and outputs: at
+ * most 2 phases, none with steps_per_pass == 2 or > KS. */
+int smi_stencil_plan_source(int x_local, int y_local, int px, int py, int rank, int timesteps,
+                            SMI_StencilPhase *phases, int max_phases, int *nphases, int neighbours[8],
+                            int *result_index);
 
 #ifdef __cplusplus
 }

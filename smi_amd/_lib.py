@@ -103,6 +103,13 @@ SIGNATURES = {
     "smi_stencil_run_residual": (I, [SMI_Comm, P, P, I, I, I, I, I, P, P, ctypes.POINTER(I)]),
     "smi_stencil_set_solve_check": (I, [I]),
     "smi_stencil_get_solve_check": (I, [ctypes.POINTER(I)]),
+    "smi_stencil_step_source": (I, [P, P, P, I, I, ctypes.POINTER(I), ctypes.POINTER(P), P, P, P, P]),
+    "smi_stencil_run_source": (I, [SMI_Comm, P, P, P, I, I, I, I, I, P, ctypes.POINTER(I)]),
+    "smi_stencil_solve_source": (I, [SMI_Comm, P, P, P, I, I, I, I, F, I, I, P, ctypes.POINTER(I), ctypes.POINTER(I),
+                                     ctypes.POINTER(F), ctypes.POINTER(I)]),
+    "smi_stencil_plan_source": (I, [I, I, I, I, I, I, P, I, ctypes.POINTER(I), ctypes.POINTER(I),
+                                    ctypes.POINTER(I)]),
+    "smi_stencil_source_max_depth": (I, [ctypes.POINTER(I)]),
 }
 
 

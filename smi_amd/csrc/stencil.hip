@@ -20,6 +20,7 @@
 #include "stencil_common.h"
 #include "stencil_resid.h"
 #include "stencil_resid_dev.h"
+#include "stencil_src.h"
 
 namespace smi {
 
@@ -37,10 +38,16 @@ namespace smi {
 // one atomic max on *resid.  Patterns of non-negative floats order like the
 // floats and every NaN pattern lies above +inf, so an unsigned max is the
 // exact max-norm and carries a NaN without a branch.
-template <int U, bool NT, bool RES>
+//
+// SRC: the update with a source term (smi_stencil_step_source),
+// out = 0.25 * ((((S + W) + E) + N) + g): one more float4 load per row, of
+// `src` at the row's own address, fetched with the row's batch, and one more
+// add per cell.  Copied cells select the centre value after the arithmetic,
+// so g never reaches a global-edge cell.
+template <int U, bool NT, bool RES, bool SRC = false>
 __device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *__restrict__ out,
                                            const SweepArgs &a, int nstrips, int nrb, int ht,
-                                           unsigned int *resid) {
+                                           unsigned int *resid, const float *__restrict__ src = nullptr) {
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
     const int lane = threadIdx.x & 63;
     const int task = __builtin_amdgcn_readfirstlane(lb * 4 + (int)(threadIdx.x >> 6));
@@ -83,9 +90,11 @@ __device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *
     auto ld4 = [&](int r) -> float4 { return *reinterpret_cast<const float4 *>(rowp(r) + c0); };
     auto ldw = [&](int r) -> float { return wbase[(size_t)r * wstride]; };
     auto lde = [&](int r) -> float { return ebase[(size_t)r * estride]; };
+    // SRC: g of row r (always a row of the tile)
+    auto ldg = [&](int r) -> float4 { return *reinterpret_cast<const float4 *>(src + (size_t)r * cols + c0); };
 
     unsigned int rmax = 0;  // RES: this lane's largest |o - c| pattern
-    auto do_row = [&](int r, float4 n, float4 c, float4 s, float ew, float ee) {
+    auto do_row = [&](int r, float4 n, float4 c, float4 s, float ew, float ee, float4 g) {
         const bool row_skip = (r == 0 && mT == SMI_SIDE_SKIP) || (r == rows - 1 && mB == SMI_SIDE_SKIP);
         const bool row_copy = (r == 0 && mT == SMI_SIDE_COPY) || (r == rows - 1 && mB == SMI_SIDE_COPY);
         float w = wave_shr1(c.w);
@@ -93,10 +102,17 @@ __device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *
         w = lane == 0 ? ew : w;
         e = lane == nl - 1 ? ee : e;
         float4 o;
-        o.x = jacobi(s.x, w, c.y, n.x);
-        o.y = jacobi(s.y, c.x, c.z, n.y);
-        o.z = jacobi(s.z, c.y, c.w, n.z);
-        o.w = jacobi(s.w, c.z, e, n.w);
+        if constexpr (SRC) {
+            o.x = jacobi_src(s.x, w, c.y, n.x, g.x);
+            o.y = jacobi_src(s.y, c.x, c.z, n.y, g.y);
+            o.z = jacobi_src(s.z, c.y, c.w, n.z, g.z);
+            o.w = jacobi_src(s.w, c.z, e, n.w, g.w);
+        } else {
+            o.x = jacobi(s.x, w, c.y, n.x);
+            o.y = jacobi(s.y, c.x, c.z, n.y);
+            o.z = jacobi(s.z, c.y, c.w, n.z);
+            o.w = jacobi(s.w, c.z, e, n.w);
+        }
         o.x = (copyL || row_copy) ? c.x : o.x;
         o.y = row_copy ? c.y : o.y;
         o.z = row_copy ? c.z : o.z;
@@ -126,16 +142,19 @@ __device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *
     float4 c = ld4(r0);
     float4 sA[U];
     float wA[U], eA[U];
+    float4 gA[SRC ? U : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int r = min(r0 + u, r1 - 1);
         sA[u] = ld4(r + 1);
         wA[u] = ldw(r);
         eA[u] = lde(r);
+        if constexpr (SRC) gA[u] = ldg(r);
     }
     for (int r = r0; r < r1; r += U) {
         float4 sB[U];
         float wB[U], eB[U];
+        float4 gB[SRC ? U : 1];
         const bool more = r + U < r1;  // uniform
         if (more) {
 #pragma unroll
@@ -144,12 +163,13 @@ __device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *
                 sB[u] = ld4(rr + 1);
                 wB[u] = ldw(rr);
                 eB[u] = lde(rr);
+                if constexpr (SRC) gB[u] = ldg(rr);
             }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (r + u < r1) {
-                do_row(r + u, n, c, sA[u], wA[u], eA[u]);
+                do_row(r + u, n, c, sA[u], wA[u], eA[u], gA[SRC ? u : 0]);
                 n = c;
                 c = sA[u];
             }
@@ -160,6 +180,7 @@ __device__ __forceinline__ void sweep_body(const float *__restrict__ in, float *
                 sA[u] = sB[u];
                 wA[u] = wB[u];
                 eA[u] = eB[u];
+                if constexpr (SRC) gA[u] = gB[u];
             }
         }
     }
@@ -184,6 +205,25 @@ __global__ __launch_bounds__(256) void sweep_res_kernel(const float *__restrict_
     sweep_body<U, NT, true>(in, out, a, nstrips, nrb, ht, resid);
 }
 
+// The source instantiations, plain and residual: `src` is a kernel argument of
+// its own, so SweepArgs and the kernels above keep their layout and code.
+template <int U, bool NT>
+__global__ __launch_bounds__(256) void sweep_src_kernel(const float *__restrict__ in,
+                                                        float *__restrict__ out, SweepArgs a,
+                                                        int nstrips, int nrb, int ht,
+                                                        const float *__restrict__ src) {
+    sweep_body<U, NT, false, true>(in, out, a, nstrips, nrb, ht, nullptr, src);
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(256) void sweep_src_res_kernel(const float *__restrict__ in,
+                                                            float *__restrict__ out, SweepArgs a,
+                                                            int nstrips, int nrb, int ht,
+                                                            const float *__restrict__ src,
+                                                            unsigned int *__restrict__ resid) {
+    sweep_body<U, NT, true, true>(in, out, a, nstrips, nrb, ht, resid, src);
+}
+
 // Cells of the tile's halo-facing sides (those with side_mask bit set),
 // computed with the true side modes (COPY / HALO); also packs the new
 // first / last column for the left / right neighbours.  One thread per cell:
@@ -191,9 +231,10 @@ __global__ __launch_bounds__(256) void sweep_res_kernel(const float *__restrict_
 // Returns the cell's |v - in| pattern for the residual variant (RES; costs the
 // one load of the centre value a computed cell does not otherwise need), 0
 // for a thread without a cell.  A corner cell is visited by two threads, which
-// a maximum does not notice.
-template <bool RES>
-__device__ __forceinline__ unsigned int edge_cell(const SweepArgs &a, int side_mask) {
+// a maximum does not notice.  SRC: a computed cell adds its cell of `src`
+// (one scalar load); a copied cell does not read it.
+template <bool RES, bool SRC = false>
+__device__ __forceinline__ unsigned int edge_cell(const SweepArgs &a, int side_mask, const float *src = nullptr) {
     const int rows = a.rows, cols = a.cols;
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     int r, c, side;
@@ -219,7 +260,10 @@ __device__ __forceinline__ unsigned int edge_cell(const SweepArgs &a, int side_m
         const float *sp = r < rows - 1 ? in + idx + cols : a.halo[1] + c;
         const float *wp = c > 0 ? in + idx - 1 : a.halo[2] + r;
         const float *ep = c < cols - 1 ? in + idx + 1 : a.halo[3] + r;
-        v = jacobi(*sp, *wp, *ep, *np);
+        if constexpr (SRC)
+            v = jacobi_src(*sp, *wp, *ep, *np, src[idx]);
+        else
+            v = jacobi(*sp, *wp, *ep, *np);
     }
     a.out[idx] = v;
     if (c == 0 && a.send_left) a.send_left[r] = v;
@@ -235,6 +279,16 @@ __global__ __launch_bounds__(256) void edge_res_kernel(SweepArgs a, int side_mas
     // every lane returns from edge_cell (with 0 if it has no cell) before the
     // wave folds: one atomic max per wave
     const unsigned int m = wave_max_u32(edge_cell<true>(a, side_mask));
+    if ((threadIdx.x & 63) == 63) resid_post(resid, m);
+}
+
+__global__ __launch_bounds__(256) void edge_src_kernel(SweepArgs a, int side_mask, const float *__restrict__ src) {
+    edge_cell<false, true>(a, side_mask, src);
+}
+
+__global__ __launch_bounds__(256) void edge_src_res_kernel(SweepArgs a, int side_mask, const float *__restrict__ src,
+                                                           unsigned int *__restrict__ resid) {
+    const unsigned int m = wave_max_u32(edge_cell<true, true>(a, side_mask, src));
     if ((threadIdx.x & 63) == 63) resid_post(resid, m);
 }
 
@@ -257,6 +311,34 @@ int check_tile(const float *in, const float *out, int rows, int cols) {
     SMI_ARG_CHECK(rows >= 1 && cols >= 4 && cols % 4 == 0, "tile must be >=1 x >=4 with y_local % 4 == 0");
     SMI_ARG_CHECK(aligned16(in) && aligned16(out), "tile buffers must be 16-byte aligned");
     return SMI_SUCCESS;
+}
+
+int check_src(const float *src, const float *buf0, const float *buf1, int rows, int cols) {
+    SMI_ARG_CHECK(src, "NULL source array");
+    SMI_ARG_CHECK(aligned16(src), "the source array must be 16-byte aligned");
+    const size_t n = (size_t)std::max(rows, 0) * (size_t)std::max(cols, 0);
+    auto overlaps = [&](const float *b) { return b && src < b + n && b < src + n; };
+    SMI_ARG_CHECK(!overlaps(buf0) && !overlaps(buf1), "the source array must not overlap a tile buffer");
+    return SMI_SUCCESS;
+}
+
+// The source kernels fetch a g row with every row of a batch: twice the float4
+// registers in flight, so 16 rows in flight run as 8 here.
+template <int U>
+static void launch_sweep_src_u(const SweepArgs &a, int nstrips, int nrb, int ht, int blocks, bool nt,
+                               const float *src, unsigned int *resid, hipStream_t s) {
+    if (resid && nt)
+        hipLaunchKernelGGL((sweep_src_res_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
+                           nstrips, nrb, ht, src, resid);
+    else if (resid)
+        hipLaunchKernelGGL((sweep_src_res_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
+                           nstrips, nrb, ht, src, resid);
+    else if (nt)
+        hipLaunchKernelGGL((sweep_src_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
+                           nstrips, nrb, ht, src);
+    else
+        hipLaunchKernelGGL((sweep_src_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
+                           nstrips, nrb, ht, src);
 }
 
 template <int U>
@@ -299,6 +381,27 @@ int launch_sweep_res(const SweepArgs &a, unsigned int *resid, hipStream_t s) {
 
 int launch_sweep(const SweepArgs &a, hipStream_t s) { return launch_sweep_res(a, nullptr, s); }
 
+// src: nullptr = launch_sweep_res, else the source instantiations
+int launch_sweep_src(const SweepArgs &a, const float *src, unsigned int *resid, hipStream_t s) {
+    if (!src) return launch_sweep_res(a, resid, s);
+    const int ht = std::max(1, g_tune.ht);
+    const int nstrips = (a.cols + 255) / 256;
+    const int nrb = (a.rows + ht - 1) / ht;
+    const long tasks = (long)nstrips * nrb;
+    const int blocks = (int)((tasks + 3) / 4);
+    int tok = -1;
+    if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_SWEEP, s, &tok, 1, (double)a.rows * a.cols));
+    switch (g_tune.u) {
+    case 1: launch_sweep_src_u<1>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
+    case 2: launch_sweep_src_u<2>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
+    case 4: launch_sweep_src_u<4>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
+    default: launch_sweep_src_u<8>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
+    }
+    SMI_HIP_CHECK(hipGetLastError());
+    if (tok >= 0) SMI_TRY(prof_end(tok, s));
+    return SMI_SUCCESS;
+}
+
 int launch_edge_res(const SweepArgs &a, int side_mask, unsigned int *resid, hipStream_t s) {
     const long cells = 2L * a.cols + 2L * a.rows;
     const int blocks = (int)((cells + 255) / 256);
@@ -314,6 +417,21 @@ int launch_edge_res(const SweepArgs &a, int side_mask, unsigned int *resid, hipS
 }
 
 int launch_edge(const SweepArgs &a, int side_mask, hipStream_t s) { return launch_edge_res(a, side_mask, nullptr, s); }
+
+int launch_edge_src(const SweepArgs &a, int side_mask, const float *src, unsigned int *resid, hipStream_t s) {
+    if (!src) return launch_edge_res(a, side_mask, resid, s);
+    const long cells = 2L * a.cols + 2L * a.rows;
+    const int blocks = (int)((cells + 255) / 256);
+    int tok = -1;
+    if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_EDGE, s, &tok));
+    if (resid)
+        hipLaunchKernelGGL(edge_src_res_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask, src, resid);
+    else
+        hipLaunchKernelGGL(edge_src_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask, src);
+    SMI_HIP_CHECK(hipGetLastError());
+    if (tok >= 0) SMI_TRY(prof_end(tok, s));
+    return SMI_SUCCESS;
+}
 
 int launch_pack_cols(const float *in, int rows, int cols, float *left, float *right, hipStream_t s) {
     hipLaunchKernelGGL(pack_cols_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, in, rows, cols, left, right);
@@ -384,6 +502,16 @@ int smi_stencil_step_residual(const float *in, float *out, int x_local, int y_lo
     SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
     SMI_ARG_CHECK(resid_bits && ((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
     return launch_sweep_res(a, resid_bits, (hipStream_t)stream);
+}
+
+int smi_stencil_step_source(const float *in, float *out, const float *src, int x_local, int y_local,
+                            const int mode[4], const float *const halo[4], float *send_left, float *send_right,
+                            unsigned int *resid_bits, SMI_Stream stream) {
+    SweepArgs a;
+    SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
+    SMI_TRY(check_src(src, in, out, x_local, y_local));
+    SMI_ARG_CHECK(((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
+    return launch_sweep_src(a, src, resid_bits, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -27,6 +27,18 @@ __device__ __forceinline__ float jacobi(float s, float w, float e, float n) {
     return __fmul_rn(0.25f, sum);
 }
 
+// The update with a source term: 0.25 * ((((S + W) + E) + N) + g), g added
+// last, before the multiply (include/smi/stencil.h).  g = -0.0f gives the bits
+// of jacobi() for every input (x + -0 = x, also for x = -0); g = +0.0f does
+// not (-0 + +0 = +0).
+__device__ __forceinline__ float jacobi_src(float s, float w, float e, float n, float g) {
+    float sum = __fadd_rn(s, w);
+    sum = __fadd_rn(sum, e);
+    sum = __fadd_rn(sum, n);
+    sum = __fadd_rn(sum, g);
+    return __fmul_rn(0.25f, sum);
+}
+
 // lane i <- lane i-1 (DPP wave_shr:1); lane 0 gets 0
 __device__ __forceinline__ float wave_shr1(float v) {
     return __builtin_bit_cast(
@@ -95,6 +107,8 @@ extern Tuning g_tune;
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 int check_tile(const float *in, const float *out, int rows, int cols);
+// a source array of the tile's shape: non-NULL, 16-byte aligned, overlapping neither buffer
+int check_src(const float *src, const float *buf0, const float *buf1, int rows, int cols);
 
 // single step (stencil.hip)
 int launch_sweep(const SweepArgs &a, hipStream_t s);
@@ -151,8 +165,9 @@ inline int check_sweep_rect(const char *who, const SweepKArgs &a) {
 // stores), else the minimal ceil(K / 4).
 __host__ __device__ constexpr int sweepk_apron_lanes(int K) { return K >= 9 ? 4 : (K + 3) / 4; }
 int launch_sweepk(int K, const SweepKArgs &a, hipStream_t s);
+// src (nullable; K <= SWEEPK_SRC_MAX of stencil_src.h, no resid): the source instantiation
 int launch_sweepk_ex(int K, const SweepKArgs &a, int ht, int reserve, bool prof, hipStream_t s,
-                     hipEvent_t stop = nullptr, unsigned int *resid = nullptr);
+                     hipEvent_t stop = nullptr, unsigned int *resid = nullptr, const float *src = nullptr);
 int sweepk_window_cols(int K);  // output columns per 256-column window
 
 // Deep K-step sweep (stencild.h / stencild.hip, SWEEPD_MIN <= K <= SWEEPD_MAX):

@@ -12,6 +12,7 @@
 
 #include "stencil_common.h"
 #include "stencil_resid.h"
+#include "stencil_src.h"
 
 namespace smi {
 
@@ -134,6 +135,7 @@ struct Tile {
     Neighbours nb;
     int side_mask;        // bit 0..3: neighbour on side top, bottom, left, right
     unsigned int *resid;  // the residual word while the final phase of a residual run is enqueued, else nullptr
+    const float *src;     // this rank's tile of the source term (a source run), else nullptr
     int cur;              // index of the buffer holding the current state
     const float *in() const { return buf[cur]; }
     float *out() const { return buf[cur ^ 1]; }
@@ -406,6 +408,35 @@ static Plan make_plan_residual(int rows, int cols, int timesteps, bool multi) {
     return p;
 }
 
+// A source run (smi_stencil_run_source; stencilk.h "Source instantiations").
+// One tile with cols >= 8: passes of min(steps per pass, SWEEPK_SRC_MAX) steps
+// under make_plan's balanced-remainder rule; a remainder of 1 or 2 steps runs
+// as single steps (there is no pair kernel with a source), and so does a
+// fusion setting below 3.  Multi-rank: single steps only, through the depth-1
+// exchange phase (no band, ring or pair kernel has a source).  At most 2
+// phases.  resid: the checked step of smi_stencil_solve_source, one single
+// residual step (the fused source sweep has no residual variant).
+static Plan make_plan_source(int cols, int timesteps, bool multi, bool resid) {
+    Plan p;
+    int K = multi || cols < 8 || resid ? 0 : std::min(g_tune.fuse, SWEEPK_SRC_MAX);
+    if (K < SWEEPK_MIN) K = 0;
+    int rest = timesteps;
+    if (K) {
+        const int passes = rest / K + 1, base = rest / passes, extra = rest % passes;
+        if (rest % K >= SWEEPK_MIN && base >= SWEEPK_MIN) {
+            p.add(base + 1, extra);
+            p.add(base, passes - extra);
+            rest = 0;
+        } else {
+            p.add(K, rest / K);
+            rest %= K;
+        }
+    }
+    p.add(1, rest);
+    p.resid_last = resid;
+    return p;
+}
+
 // single-step / pair arguments (halo views and buffers set by the phases)
 static SweepArgs step_args(const Tile &t) {
     SweepArgs a{};
@@ -434,7 +465,7 @@ static int run_single(Tile &t, const Plan &plan, unsigned int *resid, hipStream_
             if (K >= SWEEPK_MIN) {
                 ak.in = t.in();
                 ak.out = t.out();
-                SMI_TRY(launch_sweepk_ex(K, ak, 0, 0, true, s, nullptr, t.resid));
+                SMI_TRY(launch_sweepk_ex(K, ak, 0, 0, true, s, nullptr, t.resid, t.src));
             } else if (K == 2) {
                 a2.in = t.in();
                 a2.out = t.out();
@@ -442,7 +473,7 @@ static int run_single(Tile &t, const Plan &plan, unsigned int *resid, hipStream_
             } else {
                 a.in = t.in();
                 a.out = t.out();
-                SMI_TRY(launch_sweep_res(a, t.resid, s));
+                SMI_TRY(launch_sweep_src(a, t.src, t.resid, s));
             }
         }
     }
@@ -598,11 +629,12 @@ static int single_steps(Tile &t, PassSched &sc, int npass, const Halo2 &h2) {
     for (int k = 0; k < 4; ++k)
         if (inner.mode[k] == SMI_SIDE_HALO) inner.mode[k] = SMI_SIDE_SKIP;
     inner.send_left = inner.send_right = nullptr;
-    auto edge = [&](hipStream_t st, hipEvent_t) { return launch_edge_res(a, t.side_mask, t.resid, st); };
-    auto interior = [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(inner, t.resid, st); };
+    // (t.src: the source kernels, each rank reading its own tile of src)
+    auto edge = [&](hipStream_t st, hipEvent_t) { return launch_edge_src(a, t.side_mask, t.src, t.resid, st); };
+    auto interior = [&](hipStream_t st, hipEvent_t) { return launch_sweep_src(inner, t.src, t.resid, st); };
     // without overlap the full sweep reads the halos itself
     auto no_edge = [&](hipStream_t, hipEvent_t) { return (int)SMI_SUCCESS; };
-    auto full = [&](hipStream_t st, hipEvent_t) { return launch_sweep_res(a, t.resid, st); };
+    auto full = [&](hipStream_t st, hipEvent_t) { return launch_sweep_src(a, t.src, t.resid, st); };
     auto xchg1 = [&](const float *tile, hipStream_t st) {
         const HaloMsgs x = side_msgs(t, tile, 1, 1, a.halo[0], a.halo[1], a.halo[2], a.halo[3], s_left, s_right);
         return exchange(t.c, x, false, st);
@@ -684,13 +716,17 @@ static int find_comm(SMI_Comm comm, Comm **c) {
 // schedule of make_plan_residual, whose last pass's kernels also
 // max-accumulate |x_T - x_{T-1}| into *resid (timesteps >= 1; one step is the
 // checked step of smi_stencil_solve: a single residual step, stencil.hip).
+// src (nullable): a source run, the schedule of make_plan_source; with resid
+// it is the one checked step of smi_stencil_solve_source.
 static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local, int px, int py, int timesteps,
-                     SMI_Stream stream_, int *result_index, unsigned int *resid) {
+                     SMI_Stream stream_, int *result_index, unsigned int *resid, const float *src = nullptr) {
     SMI_TRY(check_grid(c, buf0, buf1, x_local, y_local, px, py));
+    if (src) SMI_TRY(check_src(src, buf0, buf1, x_local, y_local));
+    SMI_ARG_CHECK(!(src && resid) || timesteps == 1, "a source run takes its residual from one single step");
     SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
     SMI_ARG_CHECK(result_index, "NULL result_index");
     SMI_ARG_CHECK(!resid || timesteps >= 1, "a residual run takes at least one step");
-    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, nullptr, 0};
+    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, nullptr, src, 0};
 #ifdef SMI_LOOPBACK_REHEARSAL
     // Timing-rehearsal build only (never the product library; built by
     // `smi_amd/build.py --rehearsal`, driven by tools/rehearsal.py): with
@@ -708,8 +744,9 @@ static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local
         if (side_nb[k] >= 0) t.side_mask |= 1 << k;
 
     const bool multi = t.side_mask != 0;
-    const Plan plan = resid ? make_plan_residual(t.rows, t.cols, timesteps, multi)
-                            : make_plan(t.rows, t.cols, timesteps, multi);
+    const Plan plan = src     ? make_plan_source(t.cols, timesteps, multi, resid != nullptr)
+                      : resid ? make_plan_residual(t.rows, t.cols, timesteps, multi)
+                              : make_plan(t.rows, t.cols, timesteps, multi);
     *result_index = plan.passes() & 1;
     prof_break_chain();  // markers chain only between this run's own passes
     if (timesteps == 0) return SMI_SUCCESS;
@@ -826,16 +863,20 @@ int smi_stencil_deep_geometry(int rows, int cols, int K, int side_mask, int *wav
     return SMI_SUCCESS;
 }
 
-static int plan_query(bool residual, int x_local, int y_local, int px, int py, int rank, int timesteps,
+enum class PlanKind { Run, Residual, Source };
+
+static int plan_query(PlanKind kind, int x_local, int y_local, int px, int py, int rank, int timesteps,
                       SMI_StencilPhase *phases, int max_phases, int *nphases, int *neighbours, int *result_index) {
     SMI_ARG_CHECK(x_local >= 1 && y_local >= 4 && y_local % 4 == 0, "tile must be >= 1 x 4, y_local % 4 == 0");
     SMI_ARG_CHECK(px >= 1 && py >= 1 && rank >= 0 && rank < px * py, "rank outside the px x py grid");
+    const bool residual = kind == PlanKind::Residual;
     SMI_ARG_CHECK(timesteps >= (residual ? 1 : 0), residual ? "a residual run takes at least one step" : "timesteps < 0");
     SMI_ARG_CHECK(nphases && (phases || max_phases == 0), "NULL output");
     const Neighbours nb = neighbours_of(rank, px, py);
     const bool multi = nb.top >= 0 || nb.bottom >= 0 || nb.left >= 0 || nb.right >= 0;
-    const Plan p = residual ? make_plan_residual(x_local, y_local, timesteps, multi)
-                            : make_plan(x_local, y_local, timesteps, multi);
+    const Plan p = kind == PlanKind::Source ? make_plan_source(y_local, timesteps, multi, false)
+                   : residual               ? make_plan_residual(x_local, y_local, timesteps, multi)
+                                            : make_plan(x_local, y_local, timesteps, multi);
     SMI_ARG_CHECK(max_phases >= p.nph, "max_phases too small (4 always suffice)");
     for (int i = 0; i < p.nph; ++i) {
         phases[i].steps_per_pass = p.k[i];
@@ -852,14 +893,26 @@ static int plan_query(bool residual, int x_local, int y_local, int px, int py, i
 
 int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int timesteps, SMI_StencilPhase *phases,
                      int max_phases, int *nphases, int *neighbours, int *result_index) {
-    return plan_query(false, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
-                      result_index);
+    return plan_query(PlanKind::Run, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases,
+                      neighbours, result_index);
+}
+
+int smi_stencil_plan_source(int x_local, int y_local, int px, int py, int rank, int timesteps, SMI_StencilPhase *phases,
+                            int max_phases, int *nphases, int *neighbours, int *result_index) {
+    return plan_query(PlanKind::Source, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases,
+                      neighbours, result_index);
+}
+
+int smi_stencil_source_max_depth(int *k) {
+    SMI_ARG_CHECK(k, "NULL output");
+    *k = SWEEPK_SRC_MAX;
+    return SMI_SUCCESS;
 }
 
 int smi_stencil_plan_residual(int x_local, int y_local, int px, int py, int rank, int timesteps,
                               SMI_StencilPhase *phases, int max_phases, int *nphases, int *neighbours,
                               int *result_index) {
-    return plan_query(true, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
+    return plan_query(PlanKind::Residual, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
                       result_index);
 }
 
@@ -890,9 +943,20 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_
     return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, nullptr);
 }
 
-int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py, float tol,
-                      int max_steps, int check_every, SMI_Stream stream_, int *result_index, int *steps_done,
-                      float *residual, int *converged) {
+int smi_stencil_run_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local, int y_local, int px,
+                           int py, int timesteps, SMI_Stream stream_, int *result_index) {
+    // the source array first: refused before the communicator is looked up, so before any device call
+    SMI_TRY(check_src(src, buf0, buf1, x_local, y_local));
+    Comm *c = nullptr;
+    SMI_TRY(find_comm(comm, &c));
+    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, nullptr, src);
+}
+
+// smi_stencil_solve (src == nullptr) and smi_stencil_solve_source: the same
+// loop, the runs between check points and the checked step taking src.
+static int solve_steps(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local, int y_local, int px,
+                       int py, float tol, int max_steps, int check_every, SMI_Stream stream_, int *result_index,
+                       int *steps_done, float *residual, int *converged) {
     // the scalar arguments first: no device, no communicator needed to refuse them
     SMI_ARG_CHECK(tol >= 0.0f, "tol must be >= 0 and not NaN");  // false for a NaN
     SMI_ARG_CHECK(max_steps >= 0, "max_steps < 0");
@@ -911,7 +975,7 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
     float r = __builtin_inff();
     while (done < max_steps) {
         const int next = (int)std::min((long)done + check_every, (long)max_steps);
-        if (g_tune.solve_fused) {
+        if (g_tune.solve_fused && !src) {
             // smi_stencil_set_solve_check(1): the steps up to the check point
             // as one residual run, whose last K-step pass carries the residual
             SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
@@ -920,12 +984,12 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
         } else {
             // the unchecked steps, exactly as smi_stencil_run plans that many
             SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done - 1, stream_, &idx,
-                              nullptr));
+                              nullptr, src));
             cur ^= idx;
             // the checked step; its kernels run on this communicator's streams,
             // all ordered after `stream` here and joined back to it at the end
             SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
-            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, local));
+            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, local, src));
             cur ^= idx;
         }
         done = next;
@@ -944,6 +1008,21 @@ int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int 
     *residual = r;
     if (converged) *converged = r <= tol;
     return SMI_SUCCESS;
+}
+
+int smi_stencil_solve(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py, float tol,
+                      int max_steps, int check_every, SMI_Stream stream_, int *result_index, int *steps_done,
+                      float *residual, int *converged) {
+    return solve_steps(comm, buf0, buf1, nullptr, x_local, y_local, px, py, tol, max_steps, check_every, stream_,
+                       result_index, steps_done, residual, converged);
+}
+
+int smi_stencil_solve_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local, int y_local,
+                             int px, int py, float tol, int max_steps, int check_every, SMI_Stream stream_,
+                             int *result_index, int *steps_done, float *residual, int *converged) {
+    SMI_TRY(check_src(src, buf0, buf1, x_local, y_local));
+    return solve_steps(comm, buf0, buf1, src, x_local, y_local, px, py, tol, max_steps, check_every, stream_,
+                       result_index, steps_done, residual, converged);
 }
 
 }  // extern "C"

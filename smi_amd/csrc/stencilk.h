@@ -87,6 +87,35 @@
 // lanes, rows outside [o0, o1), columns outside [col_lo, col_hi)): the
 // store's hardware range check drops them, a register maximum must mask them
 // out itself (`stl` and the row's in_block below).
+//
+// Source instantiations (SRC; sweepk_src_kernel<K>, one translation unit per K
+// in stencilk_k<K>_src.hip, K = 3 .. SWEEPK_SRC_MAX of stencil_src.h).  Every
+// level adds one operand per cell, out = 0.25 * ((((S + W) + E) + N) + g),
+// g the cell of a second array `src` that travels as a kernel argument of its
+// own (SweepKArgs and the plain kernels' code stay as they are).  Level l at
+// input row t produces row t - l and needs the g row of that row, so a g row
+// is loaded with input row t (same clamped row and column, same batches, also
+// walking upwards) and stays live for K more inputs: the K rows t-1 .. t-K
+// are held in registers, G[j] = g of row t-1-j, level l reads G[l-1].
+//   Ring by rotation.  The 6-row loop body gives compile-time slots only to
+// rings of 3 or 6; G is instead written as a shift register (every input row
+// moves G[j-1] to G[j] and enters the new row at G[0]).  Inside the unrolled
+// body the shifts are register renaming and cost nothing; what remains is the
+// loop's back edge, where the K live rows return to their home registers: by
+// count 4K v_mov per 6 input rows (2/3 of a v_mov per level per row, against
+// ~14 VALU of level work; a per-row rotation would cost 4, a body unrolled to
+// lcm(6, K) rows -- 66 at K = 11 -- would not fit the instruction cache).  What
+// the compiler emits is somewhat more: sweepk_src_kernel<8> holds 1626
+// v_mov_b32 and 172 64-bit moves for 1168 level steps (all 13 walks, their
+// prologues and both loop halves: ~1.7 moves per level step, static count).
+//   Exact arithmetic only: run<ROW, CE, false>.  Under scaled levels g would
+// need a 4^(l-1) multiply per level, the multiply the scaling exists to
+// remove; so there is no guard, no second walk and no note().  The ROW_TOP /
+// ROW_BOT prologue copies and the CE column selects take the centre value, so
+// g never reaches a global-edge cell (a NaN there does not leak), and rows or
+// lanes of incomplete cones hold garbage with or without g.  There is no
+// residual variant and no band, ring or pair kernel with a source: multi-rank
+// source runs take single steps (stencil_run.cpp).
 #pragma once
 
 #include <type_traits>
@@ -163,9 +192,10 @@ enum { ROW_NONE = 0, ROW_TOP = 1, ROW_BOT = 2, ROW_FULL = 3, ROW_UP = 4 };
 // read hits L2.  Needs an even number of row blocks (launch_sweepk_ex).
 __host__ __device__ constexpr bool walks_up(int row) { return row == ROW_BOT || row == ROW_UP; }
 
-template <int K, int U, bool RES = false>
+template <int K, int U, bool RES = false, bool SRC = false>
 struct SweepK {
     static_assert(K >= SWEEPK_MIN && K <= SWEEPK_MAX, "3 <= K <= 12");
+    static_assert(!(RES && SRC), "the source sweep has no residual variant");
     static_assert(U % 3 == 0, "batch must be a multiple of the 3-slot ring");
     static constexpr int LL = sweepk_apron_lanes(K);  // lanes per window side that never store
     static constexpr int KC = 4 * LL;                  // window apron in columns (>= K)
@@ -190,6 +220,21 @@ struct SweepK {
     unsigned int *resid;
     unsigned int rmax;
     bool stl;
+    // SRC only: the source array and the g rows of the last K input rows,
+    // G[j] = g of the row of input t-1-j (a shift register, see the header)
+    const float *__restrict__ src;
+    float4 G[SRC ? K : 1];
+
+    // the g row that travels with input row t (same clamped row, same columns)
+    template <bool REV>
+    __device__ __forceinline__ float4 ldg(int t) const {
+        const int r = min(max(REV ? r_begin - t : r_begin + t, 0), rows - 1);
+        return *reinterpret_cast<const float4 *>(src + (size_t)r * cols + cl);
+    }
+    __device__ __forceinline__ void shift_g(const float4 &g) {
+        static_for<K - 1>([&](auto J) { G[K - 1 - J] = G[K - 2 - J]; });
+        G[0] = g;
+    }
 
     template <bool REV>
     __device__ __forceinline__ float4 ld(int t) const {
@@ -207,8 +252,10 @@ struct SweepK {
     // 4^(l-1) times their level-(l-1) values, so the sum ((S+W)+E)+N is
     // 4^l times the level-l value and the x 0.25 is skipped (copied edge
     // cells are scaled by 4 instead); see "Scaled levels" above.
+    // g: the cells' source term (SRC only; added last, before the multiply).
     template <int ROW, int CE, bool SC>
-    __device__ __forceinline__ float4 step(int i, const float4 &n, const float4 &c, const float4 &s) const {
+    __device__ __forceinline__ float4 step(int i, const float4 &n, const float4 &c, const float4 &s,
+                                           const float4 &g) const {
         const float w = shr1_any(c.w);
         const float e = shl1_any(c.x);
         // ((S + W) + E) element-wise, then (+ N) (and x 0.25) on packed
@@ -225,6 +272,11 @@ struct SweepK {
         }
         f32x2 o01 = f32x2{b0, b1} + f32x2{n.x, n.y};
         f32x2 o23 = f32x2{b2, b3} + f32x2{n.z, n.w};
+        if constexpr (SRC) {
+            static_assert(!(SRC && SC), "the source sweep runs the exact arithmetic only");
+            o01 = o01 + f32x2{g.x, g.y};
+            o23 = o23 + f32x2{g.z, g.w};
+        }
         if constexpr (!SC) {
             const f32x2 q = {0.25f, 0.25f};
             o01 = o01 * q;
@@ -254,10 +306,11 @@ struct SweepK {
     // row (N) and input t the lower (S); walking up they swap.
     template <int ROW, int CE, bool SC, int PH>
     __device__ __forceinline__ float4 level(int l, int t, const float4 (&P)[3]) const {
+        const float4 &g = G[SRC ? l - 1 : 0];  // the g row of row t - l (unused without SRC)
         if constexpr (walks_up(ROW))
-            return step<ROW, CE, SC>(r_begin - (t - l), P[PH], P[(PH + 2) % 3], P[(PH + 1) % 3]);
+            return step<ROW, CE, SC>(r_begin - (t - l), P[PH], P[(PH + 2) % 3], P[(PH + 1) % 3], g);
         else
-            return step<ROW, CE, SC>(r_begin + t - l, P[(PH + 1) % 3], P[(PH + 2) % 3], P[PH]);
+            return step<ROW, CE, SC>(r_begin + t - l, P[(PH + 1) % 3], P[(PH + 2) % 3], P[PH], g);
     }
 
     // Scaled-path guard: frexp exponents of every input the wave consumes
@@ -273,9 +326,9 @@ struct SweepK {
         emax = max(emax, max(e2, e3));
     }
 
-    // Input row t arrives with value x; PH = t mod 3.
+    // Input row t arrives with value x (SRC: and its g row gx); PH = t mod 3.
     template <int ROW, int CE, bool SC, int PH>
-    __device__ __forceinline__ void advance(int t, const float4 &x) {
+    __device__ __forceinline__ void advance(int t, const float4 &x, const float4 &gx) {
         W[0][PH] = x;
         if constexpr (SC) note(x);
         float4 v;
@@ -285,6 +338,7 @@ struct SweepK {
             if constexpr (l < K) W[l][PH] = v;
         });
         store_row<walks_up(ROW), SC>(t, v, W[K - 1][(PH + 2) % 3]);
+        if constexpr (SRC) shift_g(gx);
     }
 
     // Branch-free predicated store of the level-K row produced by input t:
@@ -355,12 +409,18 @@ struct SweepK {
                 }
             });
             if constexpr (t == 2 * K) store_row<REV, SC>(t, v, W[K - 1][(t + 2) % 3]);
+            if constexpr (SRC) shift_g(ldg<REV>(t));
         });
         // steady state: 2U input rows per iteration, loads one batch ahead
         const int n_in = (o1 - o0) + 2 * K;
         float4 A[U], B[U];
+        float4 GA[SRC ? U : 1], GB[SRC ? U : 1];  // SRC: the batches' g rows
 #pragma unroll
         for (int u = 0; u < U; ++u) A[u] = ld<REV>(PRO + u);
+        if constexpr (SRC) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) GA[u] = ldg<REV>(PRO + u);
+        }
         // Drain before the loop.  Without it the wait-count pass merges the
         // loads pending from the prologue into the loop header's state and
         // waits there for the store issued a few instructions earlier (a full
@@ -370,18 +430,26 @@ struct SweepK {
         for (int t = PRO; t < n_in; t += 2 * U) {
 #pragma unroll
             for (int u = 0; u < U; ++u) B[u] = ld<REV>(t + U + u);
+            if constexpr (SRC) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) GB[u] = ldg<REV>(t + U + u);
+            }
             __builtin_amdgcn_sched_barrier(0);  // issue the batch here, a whole batch ahead of its use
             static_for<U>([&](auto V) {
                 constexpr int ph = (PRO + V) % 3;
-                advance<ROW, CE, SC, ph>(t + V, A[V]);
+                advance<ROW, CE, SC, ph>(t + V, A[V], GA[SRC ? V : 0]);
             });
             if (t + U >= n_in) break;  // uniform
 #pragma unroll
             for (int u = 0; u < U; ++u) A[u] = ld<REV>(t + 2 * U + u);
+            if constexpr (SRC) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) GA[u] = ldg<REV>(t + 2 * U + u);
+            }
             __builtin_amdgcn_sched_barrier(0);
             static_for<U>([&](auto V) {
                 constexpr int ph = (PRO + U + V) % 3;
-                advance<ROW, CE, SC, ph>(t + U + V, B[V]);
+                advance<ROW, CE, SC, ph>(t + U + V, B[V], GB[SRC ? V : 0]);
             });
         }
         if constexpr (SC) {
@@ -400,7 +468,7 @@ struct SweepK {
     // blocks whose inputs leave its range
     template <int ROW, int CE>
     __device__ __forceinline__ void go() {
-        if constexpr (kScaled && ROW != ROW_FULL) {
+        if constexpr (kScaled && ROW != ROW_FULL && !SRC) {
             if (run<ROW, CE, true>()) {
                 post();
                 return;
@@ -421,10 +489,10 @@ struct SweepK {
 };
 
 // The interior task of one wave: row block rb of strip `strip`.
-template <int K, bool RES = false>
+template <int K, bool RES = false, bool SRC = false>
 __device__ __forceinline__ void sweepk_task(const SweepKArgs &a, int strip, int rb, int nrb, int lane,
-                                            unsigned int *resid = nullptr) {
-    using S = SweepK<K, 3, RES>;
+                                            unsigned int *resid = nullptr, const float *src = nullptr) {
+    using S = SweepK<K, 3, RES, SRC>;
     constexpr int SW = 256 - 2 * S::KC;  // output columns per window
     S w;
     w.in = a.in;
@@ -448,6 +516,7 @@ __device__ __forceinline__ void sweepk_task(const SweepKArgs &a, int strip, int 
         w.resid = resid;
         w.stl = st;
     }
+    if constexpr (SRC) w.src = src;
     w.copyL = a.gL && cb == 0;
     w.copyR = a.gR && cb + 4 == a.cols;
     w.gT = a.gT;
@@ -538,6 +607,51 @@ __global__ __launch_bounds__(256) SMI_SWEEPK_RES_WPE_ATTR void sweepk_res_kernel
     sweepk_task<K, true>(a, strip, rb, nrb, lane, resid);
 }
 
+// The source instantiation: the same tasks, every level adding the cell of
+// `src` ("Source instantiations" above).  Two waves per SIMD are the floor the
+// launch geometry (one round of resident waves) is tuned for.
+#ifdef SMI_SWEEPK_WPE
+#define SMI_SWEEPK_SRC_WPE_ATTR SMI_SWEEPK_WPE_ATTR
+#else
+#define SMI_SWEEPK_SRC_WPE_ATTR __attribute__((amdgpu_waves_per_eu(2, 8)))
+#endif
+template <int K>
+__global__ __launch_bounds__(256) SMI_SWEEPK_SRC_WPE_ATTR void sweepk_src_kernel(SweepKArgs a, int nstrips, int nrb,
+                                                                             const float *__restrict__ src) {
+    const int lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int lane = threadIdx.x & 63;
+    const int task = __builtin_amdgcn_readfirstlane(lb * 4 + (int)(threadIdx.x >> 6));
+    const int rb = task / nstrips;
+    const int strip = task - rb * nstrips;
+    if (rb >= nrb) return;  // wave-uniform
+    sweepk_task<K, false, true>(a, strip, rb, nrb, lane, nullptr, src);
+}
+
+template <int K>
+int sweepk_src_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, const float *src, hipStream_t s,
+                           hipEvent_t start, hipEvent_t stop) {
+    if (start || stop)
+        hipExtLaunchKernelGGL((sweepk_src_kernel<K>), dim3(blocks), dim3(256), 0, s, start, stop, 0, a, nstrips, nrb,
+                              src);
+    else
+        hipLaunchKernelGGL((sweepk_src_kernel<K>), dim3(blocks), dim3(256), 0, s, a, nstrips, nrb, src);
+    SMI_HIP_CHECK(hipGetLastError());
+    return SMI_SUCCESS;
+}
+
+template <int K>
+int sweepk_src_resident_impl() {
+    static int cached[64] = {};  // per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cached[dev]) return cached[dev];
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweepk_src_kernel<K>, 256, 0) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cached[dev] = per_cu * cus * 4;
+    return cached[dev];
+}
+
 template <int K>
 int sweepk_res_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, unsigned int *resid, hipStream_t s,
                            hipEvent_t start, hipEvent_t stop) {
@@ -609,4 +723,14 @@ int sweepk_resident_impl() {
         return sweepk_res_launch_impl<K>(a, nstrips, nrb, blocks, r, s, start, stop);                    \
     }                                                                                                    \
     int sweepk_res_resident_k##K() { return sweepk_res_resident_impl<K>(); }                             \
+    }
+
+// The source instantiations, one unit per K as well (stencilk_k<K>_src.hip).
+#define SMI_SWEEPK_SRC_INSTANCE(K)                                                                       \
+    namespace smi {                                                                                      \
+    int sweepk_src_launch_k##K(const SweepKArgs &a, int nstrips, int nrb, int blocks, const float *src,  \
+                               hipStream_t s, hipEvent_t start, hipEvent_t stop) {                       \
+        return sweepk_src_launch_impl<K>(a, nstrips, nrb, blocks, src, s, start, stop);                  \
+    }                                                                                                    \
+    int sweepk_src_resident_k##K() { return sweepk_src_resident_impl<K>(); }                             \
     }

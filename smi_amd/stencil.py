@@ -59,23 +59,43 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def _check_source(source: torch.Tensor, tile: torch.Tensor) -> None:
+    if (source.dtype != torch.float32 or source.shape != tile.shape or not source.is_cuda
+            or not source.is_contiguous()):
+        raise ValueError("source must be a contiguous float32 device tensor of the tile's shape")
+
+
+def _check_residual(residual: torch.Tensor) -> None:
+    if residual.dtype != torch.int32 or residual.numel() != 1 or not residual.is_cuda:
+        raise ValueError("residual must be a one-element int32 device tensor")
+
+
 def step(inp: torch.Tensor, out: torch.Tensor, modes=(0, 0, 0, 0), halos=(None, None, None, None),
          send_left: torch.Tensor | None = None, send_right: torch.Tensor | None = None,
-         stream=None, residual: torch.Tensor | None = None) -> None:
+         stream=None, residual: torch.Tensor | None = None, source: torch.Tensor | None = None) -> None:
     """One Jacobi step of one tile (smi_stencil_step).  modes per side
     (top, bottom, left, right): SIDE_COPY / SIDE_HALO / SIDE_SKIP.
     residual: a one-element int32 device tensor (zeroed by the caller) that
     the step max-accumulates the bit pattern of |out - inp| of the cells it
-    writes into (smi_stencil_step_residual; residual_value() decodes it)."""
+    writes into (smi_stencil_step_residual; residual_value() decodes it).
+    source: a tensor g of the tile's shape; interior cells become
+    0.25 * ((((S + W) + E) + N) + g) (smi_stencil_step_source, with or without
+    residual)."""
     X, Y = inp.shape
     m = (ctypes.c_int * 4)(*modes)
     h = (ctypes.c_void_p * 4)(*[_ptr(t) for t in halos])
+    if source is not None:
+        _check_source(source, inp)
+        if residual is not None:
+            _check_residual(residual)
+        _lib.call("smi_stencil_step_source", inp.data_ptr(), out.data_ptr(), source.data_ptr(), X, Y, m, h,
+                  _ptr(send_left), _ptr(send_right), _ptr(residual), _lib.stream_handle(stream))
+        return
     if residual is None:
         _lib.call("smi_stencil_step", inp.data_ptr(), out.data_ptr(), X, Y, m, h,
                   _ptr(send_left), _ptr(send_right), _lib.stream_handle(stream))
         return
-    if residual.dtype != torch.int32 or residual.numel() != 1 or not residual.is_cuda:
-        raise ValueError("residual must be a one-element int32 device tensor")
+    _check_residual(residual)
     _lib.call("smi_stencil_step_residual", inp.data_ptr(), out.data_ptr(), X, Y, m, h,
               _ptr(send_left), _ptr(send_right), residual.data_ptr(), _lib.stream_handle(stream))
 
@@ -86,43 +106,57 @@ def residual_value(residual: torch.Tensor) -> float:
 
 
 def solve(comm: Comm, tile: torch.Tensor, tol: float, max_steps: int, check_every: int = 20, PX: int = 1,
-          PY: int = 1, scratch: torch.Tensor | None = None, stream=None):
+          PY: int = 1, scratch: torch.Tensor | None = None, stream=None, source: torch.Tensor | None = None):
     """Jacobi steps until max |x_t - x_{t-1}| over the global grid is <= tol
     at a check point (every check_every steps and at max_steps), or max_steps
     (smi_stencil_solve; collective, synchronises with the host at every
     check).  Returns (result tensor -- tile or scratch --, steps, residual,
-    converged); the residual is a numpy float32 (exact), +inf if no step ran."""
+    converged); the residual is a numpy float32 (exact), +inf if no step ran.
+    source: this rank's tile of the source term g (smi_stencil_solve_source)."""
     if scratch is None:
         scratch = torch.empty_like(tile)
     X, Y = tile.shape
     idx, steps, conv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     res = ctypes.c_float()
-    _lib.call("smi_stencil_solve", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
-              ctypes.c_float(tol), max_steps, check_every, _lib.stream_handle(stream, tile.get_device()),
-              ctypes.byref(idx), ctypes.byref(steps), ctypes.byref(res), ctypes.byref(conv))
+    tail = (X, Y, PX, PY, ctypes.c_float(tol), max_steps, check_every, _lib.stream_handle(stream, tile.get_device()),
+            ctypes.byref(idx), ctypes.byref(steps), ctypes.byref(res), ctypes.byref(conv))
+    if source is None:
+        _lib.call("smi_stencil_solve", comm.handle, tile.data_ptr(), scratch.data_ptr(), *tail)
+    else:
+        _check_source(source, tile)
+        _lib.call("smi_stencil_solve_source", comm.handle, tile.data_ptr(), scratch.data_ptr(), source.data_ptr(),
+                  *tail)
     r = np.frombuffer(bytes(res), dtype=np.float32)[0]
     return (tile if idx.value == 0 else scratch), steps.value, r, bool(conv.value)
 
 
 def run(comm: Comm, tile: torch.Tensor, timesteps: int, PX: int, PY: int,
-        scratch: torch.Tensor | None = None, stream=None, residual: torch.Tensor | None = None) -> torch.Tensor:
+        scratch: torch.Tensor | None = None, stream=None, residual: torch.Tensor | None = None,
+        source: torch.Tensor | None = None) -> torch.Tensor:
     """The whole stencil_smi run on this rank's tile (smi_stencil_run):
     returns the tensor (tile or scratch) holding the result, like the
     reference's copy-back of half timesteps%2 (stencil_smi.cpp:344).
     residual: a one-element int32 device tensor (zeroed by the caller) that
     the run's last pass max-accumulates the bit pattern of this rank's
     max |x_T - x_{T-1}| into (smi_stencil_run_residual, timesteps >= 1;
-    rank-local, no reduce; residual_value() decodes it)."""
+    rank-local, no reduce; residual_value() decodes it).
+    source: this rank's tile of the source term g (smi_stencil_run_source;
+    not together with residual)."""
     if scratch is None:
         scratch = torch.empty_like(tile)
     X, Y = tile.shape
     idx = ctypes.c_int()
-    if residual is None:
+    if source is not None:
+        if residual is not None:
+            raise ValueError("a source run returns no residual (solve(source=...) checks with single steps)")
+        _check_source(source, tile)
+        _lib.call("smi_stencil_run_source", comm.handle, tile.data_ptr(), scratch.data_ptr(), source.data_ptr(), X, Y,
+                  PX, PY, timesteps, _lib.stream_handle(stream, tile.get_device()), ctypes.byref(idx))
+    elif residual is None:
         _lib.call("smi_stencil_run", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
                   timesteps, _lib.stream_handle(stream, tile.get_device()), ctypes.byref(idx))
     else:
-        if residual.dtype != torch.int32 or residual.numel() != 1 or not residual.is_cuda:
-            raise ValueError("residual must be a one-element int32 device tensor")
+        _check_residual(residual)
         _lib.call("smi_stencil_run_residual", comm.handle, tile.data_ptr(), scratch.data_ptr(), X, Y, PX, PY,
                   timesteps, residual.data_ptr(), _lib.stream_handle(stream, tile.get_device()), ctypes.byref(idx))
     return tile if idx.value == 0 else scratch
@@ -132,21 +166,32 @@ class _Phase(ctypes.Structure):
     _fields_ = [("steps_per_pass", ctypes.c_int), ("passes", ctypes.c_int)]
 
 
-def plan(x_local: int, y_local: int, PX: int, PY: int, rank: int, timesteps: int, residual: bool = False) -> dict:
+def plan(x_local: int, y_local: int, PX: int, PY: int, rank: int, timesteps: int, residual: bool = False,
+         source: bool = False) -> dict:
     """The schedule smi_stencil_run follows on `rank` (host only, no GPU):
     phases [(steps_per_pass, passes), ...], the neighbour ranks (top, bottom,
     left, right, tl, tr, bl, br; -1 on the global edge) and the index of the
     buffer that ends up holding the result.  residual=True: the schedule of
     run(..., residual=word) instead (smi_stencil_plan_residual), whose last
-    phase is the one pass that carries the residual."""
+    phase is the one pass that carries the residual.  source=True: the
+    schedule of run(..., source=g) (smi_stencil_plan_source)."""
+    if residual and source:
+        raise ValueError("a source run returns no residual")
     ph = (_Phase * 4)()
     n = ctypes.c_int()
     nb = (ctypes.c_int * 8)()
     ri = ctypes.c_int()
-    _lib.call("smi_stencil_plan_residual" if residual else "smi_stencil_plan", x_local, y_local, PX, PY, rank, timesteps, ph, 4, ctypes.byref(n), nb,
-              ctypes.byref(ri))
+    name = "smi_stencil_plan_source" if source else "smi_stencil_plan_residual" if residual else "smi_stencil_plan"
+    _lib.call(name, x_local, y_local, PX, PY, rank, timesteps, ph, 4, ctypes.byref(n), nb, ctypes.byref(ri))
     return {"phases": [(ph[i].steps_per_pass, ph[i].passes) for i in range(n.value)],
             "neighbours": list(nb), "result_index": ri.value}
+
+
+def source_max_depth() -> int:
+    """KS: the deepest fused pass of a source run (smi_stencil_source_max_depth; host only)."""
+    v = ctypes.c_int()
+    _lib.call("smi_stencil_source_max_depth", ctypes.byref(v))
+    return v.value
 
 
 def set_tuning(rows_per_wave: int = 0, rows_in_flight: int = 0, nontemporal: int = -1,

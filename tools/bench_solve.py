@@ -30,6 +30,15 @@ Two measurements at 8192^2 on one GPU, appended as JSON lines to --out:
                 solve, with the solve check 0 and 1 alternating, so both
                 per-check costs come from one session.
 
+  --mode source the source term (smi_stencil_run_source) against the plain
+                smi_stencil_run, alternating inside one process: one pass per
+                call at steps_per_pass 1 and KS (smi_stencil_source_max_depth),
+                device events around windows of --passes calls, every variant
+                warmed with a full window first; ms per pass, and the ratio
+                source / plain at the same depth (the source pass moves 12
+                B/cell where the plain one moves 8 and runs without scaled
+                levels).  Records go to profiles/source/ by default.
+
 Not part of bench.py; a GPU is required.
 """
 from __future__ import annotations
@@ -258,9 +267,59 @@ def mode_fused(args) -> None:
     comm.finalize()
 
 
+def mode_source(args) -> None:
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_solve needs a GPU")
+    import smi_amd
+    from smi_amd import stencil
+    N = args.size
+    comm = smi_amd.LocalGroup(1).comm(0)
+    torch.manual_seed(0)
+    tile = torch.rand((N, N), device="cuda")
+    scratch = torch.empty_like(tile)
+    g = torch.rand((N, N), device="cuda") * 1e-3
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fuse0 = stencil.get_fusion()["steps_per_pass"]
+    KS = stencil.source_max_depth()
+
+    def window(fn, n) -> float:
+        a, b = tile, scratch
+        ev0.record()
+        for _ in range(n):
+            res = fn(a, b)
+            if res is b:
+                a, b = b, a
+        ev1.record()
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) / n
+
+    for K in (1, KS):
+        stencil.set_fusion(steps_per_pass=K, rows_per_wave=-1 if K >= 3 else 0)
+        assert stencil.plan(N, N, 1, 1, 0, K, source=True)["phases"] == [(K, 1)]
+        assert stencil.plan(N, N, 1, 1, 0, K)["phases"] == [(K, 1)]
+        variants = [("run", lambda a, b: stencil.run(comm, a, K, 1, 1, scratch=b)),
+                    ("run_source", lambda a, b: stencil.run(comm, a, K, 1, 1, scratch=b, source=g))]
+        times = {name: [] for name, _ in variants}
+        for _, fn in variants:          # warm every variant at the timed shape
+            window(fn, args.passes)
+        for _ in range(args.reps):      # alternating
+            for name, fn in variants:
+                times[name].append(window(fn, args.passes))
+        sm = {name: summary(v) for name, v in times.items()}
+        for name, _ in variants:
+            emit(args.out, dict(kind="source_pass", label=args.label, variant=name, size=N, steps_per_pass=K,
+                                calls_per_window=args.passes, unit="ms per pass", **sm[name]))
+        emit(args.out, dict(kind="source_vs_plain", label=args.label, size=N, steps_per_pass=K,
+                            ratio_of_medians=sm["run_source"]["median_ms"] / sm["run"]["median_ms"],
+                            bytes_per_cell=dict(run=8, run_source=12)))
+    stencil.set_fusion(steps_per_pass=fuse0)
+    comm.finalize()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--mode", choices=("step", "solve", "fused"), required=True)
+    ap.add_argument("--mode", choices=("step", "solve", "fused", "source"), required=True)
     ap.add_argument("--lib", default=None, help="step mode: the libsmi_amd.so to time (default: this tree's)")
     ap.add_argument("--label", default="current", help="recorded with every line (e.g. parent / current)")
     ap.add_argument("--size", type=int, default=8192)
@@ -269,9 +328,13 @@ def main() -> None:
     ap.add_argument("--total-steps", type=int, default=2000, help="solve mode: steps of every run / solve")
     ap.add_argument("--passes", type=int, default=100, help="fused mode: K = 12 passes per timed window")
     ap.add_argument("--runs", type=int, default=20, help="fused mode: runs per timed window")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solve", "solve.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/solve/solve.jsonl (source mode: "
+                                                "profiles/source/source.jsonl)")
     args = ap.parse_args()
-    {"step": mode_step, "solve": mode_solve, "fused": mode_fused}[args.mode](args)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", *(("source", "source.jsonl") if args.mode == "source"
+                                                    else ("solve", "solve.jsonl")))
+    {"step": mode_step, "solve": mode_solve, "fused": mode_fused, "source": mode_source}[args.mode](args)
 
 
 if __name__ == "__main__":
