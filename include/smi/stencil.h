@@ -170,21 +170,32 @@ int smi_stencil_step_source(const float *in, float *out, const float *src, int x
  * smi_stencil_source_max_depth, with the balanced-remainder rule of
  * smi_stencil_run (a remainder >= 3 is spread over the passes); a remainder of
  * 1 or 2 runs as single steps (no pairs), and steps_per_pass < 3 runs single
- * steps only.  Multi-rank: single steps only, through the depth-1 exchange of
- * smi_stencil_run -- no multi-rank source pass is fused (there is no band,
- * ring or pair kernel with a source).  A fused source pass moves 12 B/cell per
- * up to KS steps and runs the exact arithmetic at every level. */
+ * steps only.  Multi-rank, by default: single steps only, through the depth-1
+ * exchange of smi_stencil_run.  With smi_stencil_set_source_bands(1): K-step
+ * passes like smi_stencil_run's, K = min(steps_per_pass, KS) clipped to what
+ * the tile holds (2K rows, 8 ceil(K/4) columns), the same remainder rules, the
+ * halo-facing bands by a band kernel that adds g; the depth-K halos of `src`
+ * are exchanged once per K-phase (at most twice per call) and are not kept
+ * across calls.  A fused source pass moves 12 B/cell per up to KS steps and
+ * runs the exact arithmetic at every level. */
 int smi_stencil_run_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local,
                            int y_local, int px, int py, int timesteps, SMI_Stream stream, int *result_index);
 
 /* The loop of smi_stencil_solve with the source term: source runs between the
- * check points and one single source residual step at each, the same
- * integer-max reduce and bcast (the fused source pass has no residual variant,
- * and smi_stencil_set_solve_check does not affect this function). */
+ * check points (fused across ranks too under smi_stencil_set_source_bands(1))
+ * and one single source residual step at each, the same integer-max reduce and
+ * bcast (the fused source pass has no residual variant, and
+ * smi_stencil_set_solve_check does not affect this function). */
 int smi_stencil_solve_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local,
                              int y_local, int px, int py, float tol, int max_steps, int check_every,
                              SMI_Stream stream, int *result_index, int *steps_done, float *residual,
                              int *converged);
+
+/* Multi-rank source runs.  0 (default): single steps.  1: K-step passes, K = min(steps_per_pass,
+ * KS) clipped like smi_stencil_run clips K on this tile; g's depth-K halos are exchanged once per
+ * K-phase.  Bit-identical grids for both settings.  fused = -1 keeps the setting. */
+int smi_stencil_set_source_bands(int fused);
+int smi_stencil_get_source_bands(int *fused);
 
 /* The deepest fused source pass, KS (6..12): the largest K whose sweep keeps
  * its level rings and the K live rows of g in registers at two waves per SIMD
@@ -310,7 +321,8 @@ int smi_stencil_plan_residual(int x_local, int y_local, int px, int py, int rank
                               int neighbours[8], int *result_index);
 
 /* The schedule smi_stencil_run_source follows, same arguments and outputs: at
- * most 2 phases, none with steps_per_pass == 2 or > KS. */
+ * most 2 phases, none with steps_per_pass == 2 or > KS.  A multi-rank plan
+ * follows smi_stencil_set_source_bands: [(1, timesteps)] at 0. */
 int smi_stencil_plan_source(int x_local, int y_local, int px, int py, int rank, int timesteps,
                             SMI_StencilPhase *phases, int max_phases, int *nphases, int neighbours[8],
                             int *result_index);

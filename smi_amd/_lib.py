@@ -110,6 +110,8 @@ SIGNATURES = {
     "smi_stencil_plan_source": (I, [I, I, I, I, I, I, P, I, ctypes.POINTER(I), ctypes.POINTER(I),
                                     ctypes.POINTER(I)]),
     "smi_stencil_source_max_depth": (I, [ctypes.POINTER(I)]),
+    "smi_stencil_set_source_bands": (I, [I]),
+    "smi_stencil_get_source_bands": (I, [ctypes.POINTER(I)]),
 }
 
 

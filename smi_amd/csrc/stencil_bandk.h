@@ -45,6 +45,19 @@
 // stored by exactly one of the interior sweep and this kernel (top / bottom
 // bands: all columns of the K rows; left / right bands: rows [rlo, rhi)), so
 // the two kernels' maxima into one word cover each cell exactly once.
+//
+// Source instantiations (SRC; bandk_src_kernel<K>, K = 3 .. SWEEPK_SRC_MAX, one
+// unit per K in bandk_k<K>_src.hip): the bands of a multi-rank pass of
+// smi_stencil_run_source under smi_stencil_set_source_bands(1).  Beside x[N] a
+// lane loads g[N], the source value of each of its walk positions (row walks:
+// the same two base / stride pairs; column walks: the same float4 groups), and
+// level l at input t adds g[t - l] -- the cell it produces -- last before the
+// multiply (jacobi_src).  g inside the tile is this rank's `src`; outside it a
+// second depth-K staging with the state's layout and clamping (a second
+// BandSrc), received once per K-phase.  Both travel as kernel arguments of
+// their own.  The copy rule selects the centre value, so g of a global-edge
+// cell or of a position clamped past a global edge never reaches a store.  No
+// residual and no lean variant.
 #pragma once
 
 #include "stencilk.h"
@@ -63,6 +76,14 @@ __device__ __forceinline__ float band_cell(float older, float c, float newer) {
         return jacobi(newer, shr1_any(c), shl1_any(c), older);
     else
         return jacobi(shl1_any(c), older, newer, shr1_any(c));
+}
+// the same step with the cell's source term g: jacobi_src in band_cell's argument order
+template <bool ROWWALK>
+__device__ __forceinline__ float band_cell_src(float older, float c, float newer, float g) {
+    if constexpr (ROWWALK)
+        return jacobi_src(newer, shr1_any(c), shl1_any(c), older, g);
+    else
+        return jacobi_src(shl1_any(c), older, newer, shr1_any(c), g);
 }
 
 // Source of one extended-tile cell (r, c), r in [-K, X+K), c in [-KC, Y+KC):
@@ -84,6 +105,12 @@ struct BandSrc {
         : in(a.in), top(a.h.top), bot(a.h.bot), left(a.h.left), right(a.h.right), c0(a.h.corner[0]),
           c1(a.h.corner[1]), c2(a.h.corner[2]), c3(a.h.corner[3]), X(a.rows), Y(a.cols), KC(a.kc), K(K_),
           hT(a.has[0]), hB(a.has[1]), hL(a.has[2]), hR(a.has[3]) {}
+    // the same geometry over another array of the tile's shape and its own
+    // depth-K staging (the source term g of bandk_src_kernel)
+    __device__ __forceinline__ BandSrc(const BandKArgs &a, int K_, const float *tile, const HaloK &h)
+        : in(tile), top(h.top), bot(h.bot), left(h.left), right(h.right), c0(h.corner[0]), c1(h.corner[1]),
+          c2(h.corner[2]), c3(h.corner[3]), X(a.rows), Y(a.cols), KC(a.kc), K(K_), hT(a.has[0]), hB(a.has[1]),
+          hL(a.has[2]), hR(a.has[3]) {}
     __device__ __forceinline__ const float *at(int r, int c) const {
         r = min(max(r, hT ? -K : 0), hB ? X + K - 1 : X - 1);
         c = min(max(c, hL ? -KC : 0), hR ? Y + KC - 1 : Y - 1);
@@ -119,8 +146,12 @@ struct BandW {
     // lane copies its cell every step (global edge across the walk).  out
     // also gets the level-(K-1) value of the same cell (the centre operand
     // of the last level step), which the residual instantiations use.
-    template <bool ROWWALK, bool CP, int N, typename Out>
-    __device__ __forceinline__ static void walk(const float (&x)[N], bool cp, Out &&out) {
+    // SRC: level l at input t also adds g[t - l], the source term of the
+    // cell it produces, last before the multiply (jacobi_src); the copy rule
+    // still selects the centre value, so g of a copied cell reaches nothing.
+    template <bool ROWWALK, bool CP, bool SRC, int N, int NG, typename Out>
+    __device__ __forceinline__ static void walk(const float (&x)[N], const float (&g)[NG], bool cp, Out &&out) {
+        static_assert(!SRC || NG == N, "one source value per walk position");
         float W[K][3];
         static_for<N>([&](auto T) {
             constexpr int t = T;
@@ -130,7 +161,10 @@ struct BandW {
                 constexpr int l = L + 1;
                 if constexpr (t >= 2 * l) {
                     const float c = W[l - 1][(t + 2) % 3];
-                    v = band_cell<ROWWALK>(W[l - 1][(t + 1) % 3], c, W[l - 1][t % 3]);
+                    if constexpr (SRC)
+                        v = band_cell_src<ROWWALK>(W[l - 1][(t + 1) % 3], c, W[l - 1][t % 3], g[t - l]);
+                    else
+                        v = band_cell<ROWWALK>(W[l - 1][(t + 1) % 3], c, W[l - 1][t % 3]);
                     if constexpr (CP) v = cp ? c : v;
                     if constexpr (l < K) W[l][t % 3] = v;
                     if constexpr (l == K) cK = c;
@@ -139,10 +173,12 @@ struct BandW {
             if constexpr (t >= 2 * K) out(std::integral_constant<int, t - 2 * K>{}, v, cK);
         });
     }
-
     // top (BOT = false) or bottom band: lane = column c, rows r0 + t
-    template <bool BOT, bool CP, bool RES = false>
-    __device__ __forceinline__ static void rows(const BandKArgs &a, int w, int lane, unsigned int *rmax = nullptr) {
+    // (SRC: gh / gsrc, the depth-K staging and this rank's tile of the source
+    // term, laid out and clamped exactly like a.h / a.in)
+    template <bool BOT, bool CP, bool RES = false, bool SRC = false>
+    __device__ __forceinline__ static void rows(const BandKArgs &a, int w, int lane, unsigned int *rmax = nullptr,
+                                                const HaloK *gh = nullptr, const float *gsrc = nullptr) {
         const int X = a.rows, Y = a.cols;
         const int c = w * SW - K + lane;
         const int r0 = BOT ? X - 2 * K : -K;
@@ -161,10 +197,23 @@ struct BandW {
             constexpr bool halo = BOT ? t >= 2 * K : t < K;
             x[t] = halo ? ph[(t - th) * sh] : pt[(t - tt) * st];
         });
+        // SRC: g of the same walk positions, the same two base / stride pairs
+        // over the source tile and its staging
+        float g[SRC ? NR : 1] = {};
+        if constexpr (SRC) {
+            const BandSrc gs(a, K, gsrc, *gh);
+            const float *gph = gs.at(r0 + th, c);
+            const float *gpt = gs.at(r0 + tt, c);
+            static_for<NR>([&](auto T) {
+                constexpr int t = T;
+                constexpr bool halo = BOT ? t >= 2 * K : t < K;
+                g[t] = halo ? gph[(t - th) * sh] : gpt[(t - tt) * st];
+            });
+        }
         const bool store = lane >= K && lane < 64 - K && c < Y;
         const bool cp = (!a.has[2] && c == 0) || (!a.has[3] && c == Y - 1);
         const int KCr = a.kc;
-        walk<true, CP>(x, cp, [&](auto Q, float v, float vp) {
+        walk<true, CP, SRC>(x, g, cp, [&](auto Q, float v, float vp) {
             constexpr int q = Q;  // output row r0 + K + q
             if (!store) return;
             if constexpr (RES) *rmax = max(*rmax, absdiff_bits(v, vp));
@@ -184,8 +233,9 @@ struct BandW {
     }
 
     // left (RIGHT = false) or right band: lane = row r, columns c0 + t
-    template <bool RIGHT, bool CP, bool RES = false>
-    __device__ __forceinline__ static void cols(const BandKArgs &a, int w, int lane, unsigned int *rmax = nullptr) {
+    template <bool RIGHT, bool CP, bool RES = false, bool SRC = false>
+    __device__ __forceinline__ static void cols(const BandKArgs &a, int w, int lane, unsigned int *rmax = nullptr,
+                                                const HaloK *gh = nullptr, const float *gsrc = nullptr) {
         const int X = a.rows, Y = a.cols;
         const int r = a.rlo + w * SW - K + lane;
         // float4 groups [-KC, 2KC) (right: [Y - 2KC, Y + KC)); the walk starts
@@ -203,11 +253,27 @@ struct BandW {
             const float4 &q = g[e / 4];
             x[T] = e % 4 == 0 ? q.x : e % 4 == 1 ? q.y : e % 4 == 2 ? q.z : q.w;
         });
+        // SRC: g of the same walk positions, the same float4 groups over the
+        // source tile and its staging
+        float gx[SRC ? NC : 1] = {};
+        if constexpr (SRC) {
+            const BandSrc gs(a, K, gsrc, *gh);
+            float4 gg[G4];
+            static_for<G4>([&](auto G) {
+                constexpr int j = G;
+                gg[j] = *reinterpret_cast<const float4 *>(gs.at(r, g0 + 4 * j));
+            });
+            static_for<NC>([&](auto T) {
+                constexpr int e = (KC - K) + T;
+                const float4 &q = gg[e / 4];
+                gx[T] = e % 4 == 0 ? q.x : e % 4 == 1 ? q.y : e % 4 == 2 ? q.z : q.w;
+            });
+        }
         const bool store = lane >= K && lane < 64 - K && r < a.rhi;
         const bool cp = (!a.has[0] && r == 0) || (!a.has[1] && r == X - 1);
         float o[KC];
         unsigned int m = 0;  // RES: max |v_K - v_{K-1}| over this lane's KC cells
-        walk<false, CP>(x, cp, [&](auto Q, float v, float vp) {
+        walk<false, CP, SRC>(x, gx, cp, [&](auto Q, float v, float vp) {
             o[Q] = v;
             if constexpr (RES) m = max(m, absdiff_bits(v, vp));
         });
@@ -234,8 +300,9 @@ struct BandW {
 // Band segment wv: one wave per 64-cell run of a band; segments [first[0],
 // first[1]) top, [first[1], first[2]) bottom, [first[2], first[3]) left,
 // [first[3], first[4]) right.
-template <int K, bool RES = false>
-__device__ __forceinline__ void bandk_wave(const BandKArgs &a, int wv, int lane, unsigned int *rmax = nullptr) {
+template <int K, bool RES = false, bool SRC = false>
+__device__ __forceinline__ void bandk_wave(const BandKArgs &a, int wv, int lane, unsigned int *rmax = nullptr,
+                                           const HaloK *gh = nullptr, const float *gsrc = nullptr) {
     using B = BandW<K>;
     const int band = (wv >= a.first[1]) + (wv >= a.first[2]) + (wv >= a.first[3]);
     // (no dynamic index into the kernel argument: that would copy it to scratch)
@@ -246,16 +313,20 @@ __device__ __forceinline__ void bandk_wave(const BandKArgs &a, int wv, int lane,
         const int c_lo = w * B::SW - K, c_hi = c_lo + 63;
         const bool cp = (!a.has[2] && c_lo <= 0 && c_hi >= 0) || (!a.has[3] && c_lo <= Y - 1 && c_hi >= Y - 1);
         if (band == 0)
-            cp ? B::template rows<false, true, RES>(a, w, lane, rmax) : B::template rows<false, false, RES>(a, w, lane, rmax);
+            cp ? B::template rows<false, true, RES, SRC>(a, w, lane, rmax, gh, gsrc)
+               : B::template rows<false, false, RES, SRC>(a, w, lane, rmax, gh, gsrc);
         else
-            cp ? B::template rows<true, true, RES>(a, w, lane, rmax) : B::template rows<true, false, RES>(a, w, lane, rmax);
+            cp ? B::template rows<true, true, RES, SRC>(a, w, lane, rmax, gh, gsrc)
+               : B::template rows<true, false, RES, SRC>(a, w, lane, rmax, gh, gsrc);
     } else {
         const int r_lo = a.rlo + w * B::SW - K, r_hi = r_lo + 63;
         const bool cp = (!a.has[0] && r_lo <= 0 && r_hi >= 0) || (!a.has[1] && r_lo <= X - 1 && r_hi >= X - 1);
         if (band == 2)
-            cp ? B::template cols<false, true, RES>(a, w, lane, rmax) : B::template cols<false, false, RES>(a, w, lane, rmax);
+            cp ? B::template cols<false, true, RES, SRC>(a, w, lane, rmax, gh, gsrc)
+               : B::template cols<false, false, RES, SRC>(a, w, lane, rmax, gh, gsrc);
         else
-            cp ? B::template cols<true, true, RES>(a, w, lane, rmax) : B::template cols<true, false, RES>(a, w, lane, rmax);
+            cp ? B::template cols<true, true, RES, SRC>(a, w, lane, rmax, gh, gsrc)
+               : B::template cols<true, false, RES, SRC>(a, w, lane, rmax, gh, gsrc);
     }
 }
 
@@ -288,6 +359,21 @@ __global__ __launch_bounds__(256) void bandk_res_kernel(BandKArgs a, unsigned in
     // inside a segment end at its inlined call): one filtered atomic per wave
     rmax = wave_max_u32(rmax);
     if ((threadIdx.x & 63) == 63) resid_post(resid, rmax);
+}
+
+// The source instantiation (K = 3 .. SWEEPK_SRC_MAX, one unit per K in
+// bandk_k<K>_src.hip): the bands of a multi-rank pass of smi_stencil_run_source,
+// every level adding the cell's source term (walk's SRC).  The same segments,
+// stores and tee as bandk_kernel.  g inside the extended tile comes from this
+// rank's `src`, outside it from gh: a second depth-K staging, filled by one
+// exchange of g per K-phase (stencil_run.cpp) -- kernel arguments of their
+// own, BandKArgs carries the state only.  No residual and no lean variant.
+template <int K>
+__global__ __launch_bounds__(256) void bandk_src_kernel(BandKArgs a, HaloK gh, const float *__restrict__ src) {
+    const int waves = gridDim.x * 4;
+    const int wv0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    for (int wv = wv0; wv < a.first[4]; wv += waves)  // wave-uniform
+        bandk_wave<K, false, true>(a, wv, threadIdx.x & 63, nullptr, &gh, src);
 }
 
 // ---------------------------------------------------------------------------
@@ -637,9 +723,29 @@ int bandk_res_launch_impl(const BandKArgs &a, int waves, unsigned int *resid, hi
     return SMI_SUCCESS;
 }
 
+template <int K>
+int bandk_src_launch_impl(const BandKArgs &a, const HaloK &gh, const float *src, int waves, hipStream_t s,
+                          hipEvent_t start, hipEvent_t stop) {
+    if (start || stop)
+        hipExtLaunchKernelGGL((bandk_src_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, start, stop, 0, a, gh, src);
+    else
+        hipLaunchKernelGGL((bandk_src_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, a, gh, src);
+    SMI_HIP_CHECK(hipGetLastError());
+    return SMI_SUCCESS;
+}
+
 }  // namespace smi
 
-#define SMI_BANDK_RES_INSTANCE(K)                                                                        \
+// The source instantiations, one unit per K (bandk_k<K>_src.hip).
+#define SMI_BANDK_SRC_INSTANCE(K)                                                                        \
+    namespace smi {                                                                                      \
+    int bandk_src_launch_k##K(const BandKArgs &a, const HaloK &gh, const float *src, int waves,          \
+                              hipStream_t s, hipEvent_t start, hipEvent_t stop) {                        \
+        return bandk_src_launch_impl<K>(a, gh, src, waves, s, start, stop);                              \
+    }                                                                                                    \
+    }
+
+#define SMI_BANDK_RES_INSTANCE(K)                                                                       \
     namespace smi {                                                                                      \
     int bandk_res_launch_k##K(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s,         \
                               hipEvent_t start, hipEvent_t stop) {                                       \

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "stencil_common.h"
+#include "stencil_src.h"
 
 namespace smi {
 
@@ -27,6 +28,16 @@ static constexpr decltype(bandl_launch_k13) *kBandL[] = {SMI_FOR_K_13_20(SMI_BAN
 SMI_FOR_K_3_12(SMI_BANDK_RES_DECL)
 #define SMI_BANDK_RES_ENTRY(K) bandk_res_launch_k##K,
 static constexpr decltype(bandk_res_launch_k3) *kBandKRes[] = {SMI_FOR_K_3_12(SMI_BANDK_RES_ENTRY)};
+
+// the source instantiations (bandk_k<K>_src.hip), [K - SWEEPK_MIN], K = 3 .. SWEEPK_SRC_MAX
+#define SMI_BANDK_SRC_DECL(K)                                                                       \
+    int bandk_src_launch_k##K(const BandKArgs &a, const HaloK &gh, const float *src, int waves,     \
+                              hipStream_t s, hipEvent_t start, hipEvent_t stop);
+SMI_FOR_K_SRC(SMI_BANDK_SRC_DECL)
+#define SMI_BANDK_SRC_ENTRY(K) bandk_src_launch_k##K,
+static constexpr decltype(bandk_src_launch_k3) *kBandKSrc[] = {SMI_FOR_K_SRC(SMI_BANDK_SRC_ENTRY)};
+static_assert(sizeof(kBandKSrc) / sizeof(kBandKSrc[0]) == SWEEPK_SRC_MAX - SWEEPK_MIN + 1,
+              "SMI_FOR_K_SRC lists K = 3 .. SWEEPK_SRC_MAX");
 
 static int compute_units() {
     static int cached[64] = {};
@@ -112,6 +123,32 @@ int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t st
     } else {
         SMI_TRY(kBandK[K - SWEEPK_MIN](a, n, s, start, kstop));
     }
+    if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
+    return SMI_SUCCESS;
+}
+
+// The bands of a source pass (bandk_src_kernel): launch_bandk's one wave per
+// segment or max_waves looping waves, timed the same way under its own
+// profiling entry.  There is no lean and no residual variant.
+int launch_bandk_src(int K, BandKArgs a, const HaloK &g_halo, const float *src, int max_waves, hipStream_t s,
+                     hipEvent_t stop) {
+    SMI_ARG_CHECK(src, "bandk: NULL source");
+    SMI_ARG_CHECK(K >= SWEEPK_MIN && K <= SWEEPK_SRC_MAX,
+                  "bandk: the source pass runs K = 3.." + std::to_string(SWEEPK_SRC_MAX));
+    SMI_TRY(plan_bands(K, &a, false));
+    const int segs = a.first[4];
+    if (segs == 0) {
+        if (stop) SMI_HIP_CHECK(hipEventRecord(stop, s));
+        return SMI_SUCCESS;
+    }
+    const int n = max_waves > 0 ? std::min(segs, std::max(4, max_waves)) : segs;
+    hipEvent_t start = nullptr, kstop = stop, after = nullptr;
+    int tok = -1;
+    if (prof_enabled()) {
+        SMI_TRY(prof_launch(SMI_PROF_STENCIL_EDGE, &tok, K, 0.0, &start, &kstop));
+        after = stop;
+    }
+    SMI_TRY(kBandKSrc[K - SWEEPK_MIN](a, g_halo, src, n, s, start, kstop));
     if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
     return SMI_SUCCESS;
 }

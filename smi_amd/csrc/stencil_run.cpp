@@ -408,17 +408,26 @@ static Plan make_plan_residual(int rows, int cols, int timesteps, bool multi) {
     return p;
 }
 
+// smi_stencil_set_source_bands: 1 = multi-rank source runs take K-step passes
+// (0: single steps)
+static int g_source_bands = 0;
+
 // A source run (smi_stencil_run_source; stencilk.h "Source instantiations").
 // One tile with cols >= 8: passes of min(steps per pass, SWEEPK_SRC_MAX) steps
 // under make_plan's balanced-remainder rule; a remainder of 1 or 2 steps runs
 // as single steps (there is no pair kernel with a source), and so does a
-// fusion setting below 3.  Multi-rank: single steps only, through the depth-1
-// exchange phase (no band, ring or pair kernel has a source).  At most 2
-// phases.  resid: the checked step of smi_stencil_solve_source, one single
-// residual step (the fused source sweep has no residual variant).
-static Plan make_plan_source(int cols, int timesteps, bool multi, bool resid) {
+// fusion setting below 3.  Multi-rank: single steps through the depth-1
+// exchange phase by default; with smi_stencil_set_source_bands(1) the same
+// rule at the K the tile holds (tile_fuse: 2K x 2KC), the bands by
+// bandk_src_kernel, and a remainder of 1 or 2 as single steps in a phase of
+// their own.  At most 2 phases.  resid: the checked step of
+// smi_stencil_solve_source, one single residual step (the fused source sweep
+// and band kernel have no residual variant).
+static Plan make_plan_source(int rows, int cols, int timesteps, bool multi, bool resid) {
     Plan p;
-    int K = multi || cols < 8 || resid ? 0 : std::min(g_tune.fuse, SWEEPK_SRC_MAX);
+    int K = 0;
+    if (cols >= 8 && !resid && (!multi || g_source_bands))
+        K = std::min(multi ? tile_fuse(rows, cols, true) : g_tune.fuse, SWEEPK_SRC_MAX);
     if (K < SWEEPK_MIN) K = 0;
     int rest = timesteps;
     if (K) {
@@ -567,7 +576,11 @@ struct PassSched {
 };
 
 // ---- K steps per pass (depth-K halos)
-static int k_passes(Tile &t, PassSched &sc, int K, int npass, const HaloK &hk) {
+// t.src (a source run): the source instantiations of both kernels, and g's own
+// depth-K halos in gk -- a second staging, exchanged here once for the phase
+// (g is constant over a run, but the phases differ in depth; nothing is kept
+// across calls: the caller may change src between runs).
+static int k_passes(Tile &t, PassSched &sc, int K, int npass, const HaloK &hk, const HaloK &gk) {
     SweepKArgs ak = interior_rect(t.rows, t.cols, K, t.side_mask);
     BandKArgs bk{};
     bk.rows = t.rows;
@@ -577,14 +590,21 @@ static int k_passes(Tile &t, PassSched &sc, int K, int npass, const HaloK &hk) {
     bk.h = hk;
     // t.resid: the residual pass -- both kernels' residual instantiations, one word
     auto ring = [&](hipStream_t st, hipEvent_t stop) {
+        if (t.src) return launch_bandk_src(K, bk, gk, t.src, g_tune.band_reserve, st, stop);
         return launch_bandk(K, bk, g_tune.band_reserve, st, stop, t.resid);
     };
     auto interior = [&](hipStream_t st, hipEvent_t stop) {
-        return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop, t.resid);
+        return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop, t.resid, t.src);
     };
     auto xchgk = [&](const float *tile, hipStream_t st) { return exchange(t.c, msgsk(t, tile, K, hk), true, st); };
     SMI_TRY(launch_packk(t.in(), t.rows, t.cols, K, hk, sc.cs));
     SMI_TRY(xchgk(t.in(), sc.cs));
+    if (t.src) {
+        // g's halos, directly behind the state's on the comm stream: every
+        // rank posts the two exchanges in this order
+        SMI_TRY(launch_packk(t.src, t.rows, t.cols, K, gk, sc.cs));
+        SMI_TRY(exchange(t.c, msgsk(t, t.src, K, gk), true, sc.cs));
+    }
     sc.kpass = 0;
     for (int p = 0; p < npass; ++p, t.cur ^= 1) {
         bk.in = ak.in = t.in();
@@ -672,8 +692,9 @@ static int run_multi(Tile &t, const Plan &plan, unsigned int *resid, hipStream_t
 
     int kmax = 0;  // deepest K-step phase (sizes the depth-K staging)
     for (int i = 0; i < plan.nph; ++i) kmax = std::max(kmax, plan.k[i] >= SWEEPK_MIN ? plan.k[i] : 0);
-    const size_t need2 = halo2_elems(t.rows, t.cols);
-    SMI_TRY(ensure_halo(c, need2 + halok_elems(t.rows, t.cols, kmax)));
+    // a source run with a K-phase: g's depth-K staging behind the state's
+    const size_t need2 = halo2_elems(t.rows, t.cols), needk = halok_elems(t.rows, t.cols, kmax);
+    SMI_TRY(ensure_halo(c, need2 + needk + (t.src ? needk : 0)));
     const Halo2 h2 = halo2_layout(c->halo, t.rows, t.cols);
 
     for (int ph = 0; ph < plan.nph; ++ph) {
@@ -681,7 +702,8 @@ static int run_multi(Tile &t, const Plan &plan, unsigned int *resid, hipStream_t
         t.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
         SMI_TRY(sc.phase_start());
         if (K >= SWEEPK_MIN)
-            SMI_TRY(k_passes(t, sc, K, npass, halok_layout(c->halo + need2, t.rows, t.cols, kmax)));
+            SMI_TRY(k_passes(t, sc, K, npass, halok_layout(c->halo + need2, t.rows, t.cols, kmax),
+                             halok_layout(c->halo + need2 + (t.src ? needk : 0), t.rows, t.cols, kmax)));
         else if (K == 2)
             SMI_TRY(pair_passes(t, sc, npass, h2));
         else
@@ -744,7 +766,7 @@ static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local
         if (side_nb[k] >= 0) t.side_mask |= 1 << k;
 
     const bool multi = t.side_mask != 0;
-    const Plan plan = src     ? make_plan_source(t.cols, timesteps, multi, resid != nullptr)
+    const Plan plan = src     ? make_plan_source(t.rows, t.cols, timesteps, multi, resid != nullptr)
                       : resid ? make_plan_residual(t.rows, t.cols, timesteps, multi)
                               : make_plan(t.rows, t.cols, timesteps, multi);
     *result_index = plan.passes() & 1;
@@ -874,7 +896,7 @@ static int plan_query(PlanKind kind, int x_local, int y_local, int px, int py, i
     SMI_ARG_CHECK(nphases && (phases || max_phases == 0), "NULL output");
     const Neighbours nb = neighbours_of(rank, px, py);
     const bool multi = nb.top >= 0 || nb.bottom >= 0 || nb.left >= 0 || nb.right >= 0;
-    const Plan p = kind == PlanKind::Source ? make_plan_source(y_local, timesteps, multi, false)
+    const Plan p = kind == PlanKind::Source ? make_plan_source(x_local, y_local, timesteps, multi, false)
                    : residual               ? make_plan_residual(x_local, y_local, timesteps, multi)
                                             : make_plan(x_local, y_local, timesteps, multi);
     SMI_ARG_CHECK(max_phases >= p.nph, "max_phases too small (4 always suffice)");
@@ -924,6 +946,17 @@ int smi_stencil_set_solve_check(int fused) {
 
 int smi_stencil_get_solve_check(int *fused) {
     if (fused) *fused = g_tune.solve_fused;
+    return SMI_SUCCESS;
+}
+
+int smi_stencil_set_source_bands(int fused) {
+    SMI_ARG_CHECK(fused <= 1, "source bands: 0 (multi-rank source runs take single steps) or 1 (K-step passes)");
+    if (fused >= 0) g_source_bands = fused;
+    return SMI_SUCCESS;
+}
+
+int smi_stencil_get_source_bands(int *fused) {
+    if (fused) *fused = g_source_bands;
     return SMI_SUCCESS;
 }
 

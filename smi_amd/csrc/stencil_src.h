@@ -22,4 +22,11 @@ constexpr int SWEEPK_SRC_MAX = 9;
 int launch_sweep_src(const SweepArgs &a, const float *src, unsigned int *resid, hipStream_t s);
 int launch_edge_src(const SweepArgs &a, int side_mask, const float *src, unsigned int *resid, hipStream_t s);
 
+// The bands of a multi-rank source pass (bandk_src_kernel<K>, bandk_k<K>_src.hip,
+// K = 3 .. SWEEPK_SRC_MAX): launch_bandk with the source term.  src: this
+// rank's tile of g; g_halo: g's depth-K staging (the layout of a.h), received
+// once per K-phase.  max_waves / stop as launch_bandk.
+int launch_bandk_src(int K, BandKArgs a, const HaloK &g_halo, const float *src, int max_waves, hipStream_t s,
+                     hipEvent_t stop = nullptr);
+
 }  // namespace smi

@@ -114,8 +114,11 @@
 // ROW_BOT prologue copies and the CE column selects take the centre value, so
 // g never reaches a global-edge cell (a NaN there does not leak), and rows or
 // lanes of incomplete cones hold garbage with or without g.  There is no
-// residual variant and no band, ring or pair kernel with a source: multi-rank
-// source runs take single steps (stencil_run.cpp).
+// residual variant and no ring or pair kernel with a source.  Multi-rank source
+// runs take single steps by default; under smi_stencil_set_source_bands(1) this
+// kernel is the interior of their K-step passes (an interior rectangle's cone
+// never leaves the tile, so it needs no g halo) beside bandk_src_kernel<K>
+// (stencil_bandk.h), which reads g's depth-K halos (stencil_run.cpp).
 #pragma once
 
 #include <type_traits>

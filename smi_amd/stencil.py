@@ -273,6 +273,20 @@ def get_solve_check() -> int:
     return v.value
 
 
+def set_source_bands(fused: int = -1) -> None:
+    """Multi-rank source runs (same grid either way): 0 = single steps
+    (default), 1 = K-step passes with a source band kernel, g's depth-K halos
+    exchanged once per K-phase.  plan(source=True) follows the setting.  -1
+    keeps it (smi_stencil_set_source_bands)."""
+    _lib.call("smi_stencil_set_source_bands", fused)
+
+
+def get_source_bands() -> int:
+    v = ctypes.c_int()
+    _lib.call("smi_stencil_get_source_bands", ctypes.byref(v))
+    return v.value
+
+
 def deep_geometry(rows: int, cols: int, k: int, side_mask: int = 0) -> dict:
     """The rotating-ring sweep's work split for one K-step pass (host only;
     with no device set the launch's waves first: set_deep(waves=...))."""
