@@ -1,3 +1,3 @@
 // bandk_k4_src.hip -- bandk_src_kernel<4>, the source instantiation (stencil_bandk.h)
 #include "stencil_bandk.h"
-SMI_BANDK_SRC_INSTANCE(4)
+SMI_BANDK_INSTANCE(4, Src)

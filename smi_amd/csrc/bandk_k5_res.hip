@@ -1,3 +1,3 @@
 // bandk_k5_res.hip -- bandk_res_kernel<5>, the residual instantiation (stencil_bandk.h)
 #include "stencil_bandk.h"
-SMI_BANDK_RES_INSTANCE(5)
+SMI_BANDK_INSTANCE(5, Res)

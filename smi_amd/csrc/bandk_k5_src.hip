@@ -1,3 +1,3 @@
 // bandk_k5_src.hip -- bandk_src_kernel<5>, the source instantiation (stencil_bandk.h)
 #include "stencil_bandk.h"
-SMI_BANDK_SRC_INSTANCE(5)
+SMI_BANDK_INSTANCE(5, Src)

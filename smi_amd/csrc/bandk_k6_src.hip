@@ -1,3 +1,3 @@
 // bandk_k6_src.hip -- bandk_src_kernel<6>, the source instantiation (stencil_bandk.h)
 #include "stencil_bandk.h"
-SMI_BANDK_SRC_INSTANCE(6)
+SMI_BANDK_INSTANCE(6, Src)

@@ -1,3 +1,3 @@
 // bandk_k8.hip -- bandk_kernel<8> (stencil_bandk.h)
 #include "stencil_bandk.h"
-SMI_BANDK_INSTANCE(8)
+SMI_BANDK_INSTANCE(8, Plain)

@@ -1,3 +1,3 @@
 // bandk_k8_res.hip -- bandk_res_kernel<8>, the residual instantiation (stencil_bandk.h)
 #include "stencil_bandk.h"
-SMI_BANDK_RES_INSTANCE(8)
+SMI_BANDK_INSTANCE(8, Res)

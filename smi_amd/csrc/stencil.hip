@@ -18,9 +18,7 @@
 #include <algorithm>
 
 #include "stencil_common.h"
-#include "stencil_resid.h"
 #include "stencil_resid_dev.h"
-#include "stencil_src.h"
 
 namespace smi {
 
@@ -322,113 +320,80 @@ int check_src(const float *src, const float *buf0, const float *buf1, int rows, 
     return SMI_SUCCESS;
 }
 
-// The source kernels fetch a g row with every row of a batch: twice the float4
-// registers in flight, so 16 rows in flight run as 8 here.
-template <int U>
-static void launch_sweep_src_u(const SweepArgs &a, int nstrips, int nrb, int ht, int blocks, bool nt,
-                               const float *src, unsigned int *resid, hipStream_t s) {
-    if (resid && nt)
-        hipLaunchKernelGGL((sweep_src_res_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht, src, resid);
-    else if (resid)
-        hipLaunchKernelGGL((sweep_src_res_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht, src, resid);
-    else if (nt)
-        hipLaunchKernelGGL((sweep_src_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht, src);
-    else
-        hipLaunchKernelGGL((sweep_src_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht, src);
+int resident_waves(const void *kernel, int (&cache)[64]) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cache[dev]) return cache[dev];
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cache[dev] = per_cu * cus * 4;
+    return cache[dev];
 }
 
+// strips x row blocks of `ht` rows of a single-step sweep (four tasks per workgroup)
+struct SweepGeom {
+    int nstrips, nrb, ht;
+};
+
+// the kernel of (U, NT, kind).  The source kernels exist for U <= 8 only
+// (launch_sweep below).
+template <int U, bool NT>
+static int launch_sweep_unt(const SweepArgs &a, const SweepGeom &g, const Variant &v, hipStream_t s) {
+    const dim3 grid((unsigned int)(((long)g.nstrips * g.nrb + 3) / 4));
+    auto go = [&](auto kernel, auto... extra) {
+        return launch_kernel(kernel, grid, 0, s, nullptr, nullptr, a.in, a.out, a, g.nstrips, g.nrb, g.ht, extra...);
+    };
+    if constexpr (U <= 8) {
+        if (v.kind() == Kind::SrcRes) return go(sweep_src_res_kernel<U, NT>, v.src, v.resid);
+        if (v.kind() == Kind::Src) return go(sweep_src_kernel<U, NT>, v.src);
+    }
+    if (v.kind() == Kind::Res) return go(sweep_res_kernel<U, NT>, v.resid);
+    SMI_ARG_CHECK(v.kind() == Kind::Plain, "sweep: no source kernel at this many rows in flight");
+    return go(sweep_kernel<U, NT>);
+}
 template <int U>
-static void launch_sweep_u(const SweepArgs &a, int nstrips, int nrb, int ht, int blocks, bool nt,
-                           unsigned int *resid, hipStream_t s) {
-    if (resid && nt)
-        hipLaunchKernelGGL((sweep_res_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht, resid);
-    else if (resid)
-        hipLaunchKernelGGL((sweep_res_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht, resid);
-    else if (nt)
-        hipLaunchKernelGGL((sweep_kernel<U, true>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht);
-    else
-        hipLaunchKernelGGL((sweep_kernel<U, false>), dim3(blocks), dim3(256), 0, s, a.in, a.out, a,
-                           nstrips, nrb, ht);
+static int launch_sweep_u(const SweepArgs &a, const SweepGeom &g, const Variant &v, hipStream_t s) {
+    return g_tune.nt ? launch_sweep_unt<U, true>(a, g, v, s) : launch_sweep_unt<U, false>(a, g, v, s);
 }
 
-// resid: nullptr = the plain kernels, else the residual variants
-int launch_sweep_res(const SweepArgs &a, unsigned int *resid, hipStream_t s) {
+int launch_sweep(const SweepArgs &a, const Variant &v, hipStream_t s) {
     const int ht = std::max(1, g_tune.ht);
-    const int nstrips = (a.cols + 255) / 256;
-    const int nrb = (a.rows + ht - 1) / ht;
-    const long tasks = (long)nstrips * nrb;
-    const int blocks = (int)((tasks + 3) / 4);
+    const SweepGeom g{(a.cols + 255) / 256, (a.rows + ht - 1) / ht, ht};
     int tok = -1;
     if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_SWEEP, s, &tok, 1, (double)a.rows * a.cols));
-    switch (g_tune.u) {
-    case 1: launch_sweep_u<1>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
-    case 2: launch_sweep_u<2>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
-    case 8: launch_sweep_u<8>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
-    case 16: launch_sweep_u<16>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
-    default: launch_sweep_u<4>(a, nstrips, nrb, ht, blocks, g_tune.nt, resid, s); break;
+    // Rows in flight.  The source kernels fetch a g row with every row of a
+    // batch: twice the float4 registers in flight, so 16 rows in flight run
+    // as 8 there; any other setting means 8 for them and 4 for the plain ones.
+    int u = g_tune.u;
+    if (v.src)
+        u = u == 1 || u == 2 || u == 4 ? u : 8;
+    else
+        u = u == 1 || u == 2 || u == 8 || u == 16 ? u : 4;
+    switch (u) {
+    case 1: SMI_TRY(launch_sweep_u<1>(a, g, v, s)); break;
+    case 2: SMI_TRY(launch_sweep_u<2>(a, g, v, s)); break;
+    case 4: SMI_TRY(launch_sweep_u<4>(a, g, v, s)); break;
+    case 8: SMI_TRY(launch_sweep_u<8>(a, g, v, s)); break;
+    default: SMI_TRY(launch_sweep_u<16>(a, g, v, s)); break;
     }
-    SMI_HIP_CHECK(hipGetLastError());
     if (tok >= 0) SMI_TRY(prof_end(tok, s));
     return SMI_SUCCESS;
 }
 
-int launch_sweep(const SweepArgs &a, hipStream_t s) { return launch_sweep_res(a, nullptr, s); }
-
-// src: nullptr = launch_sweep_res, else the source instantiations
-int launch_sweep_src(const SweepArgs &a, const float *src, unsigned int *resid, hipStream_t s) {
-    if (!src) return launch_sweep_res(a, resid, s);
-    const int ht = std::max(1, g_tune.ht);
-    const int nstrips = (a.cols + 255) / 256;
-    const int nrb = (a.rows + ht - 1) / ht;
-    const long tasks = (long)nstrips * nrb;
-    const int blocks = (int)((tasks + 3) / 4);
-    int tok = -1;
-    if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_SWEEP, s, &tok, 1, (double)a.rows * a.cols));
-    switch (g_tune.u) {
-    case 1: launch_sweep_src_u<1>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
-    case 2: launch_sweep_src_u<2>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
-    case 4: launch_sweep_src_u<4>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
-    default: launch_sweep_src_u<8>(a, nstrips, nrb, ht, blocks, g_tune.nt, src, resid, s); break;
-    }
-    SMI_HIP_CHECK(hipGetLastError());
-    if (tok >= 0) SMI_TRY(prof_end(tok, s));
-    return SMI_SUCCESS;
-}
-
-int launch_edge_res(const SweepArgs &a, int side_mask, unsigned int *resid, hipStream_t s) {
+int launch_edge(const SweepArgs &a, int side_mask, const Variant &v, hipStream_t s) {
     const long cells = 2L * a.cols + 2L * a.rows;
-    const int blocks = (int)((cells + 255) / 256);
+    const dim3 grid((unsigned int)((cells + 255) / 256));
     int tok = -1;
     if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_EDGE, s, &tok));
-    if (resid)
-        hipLaunchKernelGGL(edge_res_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask, resid);
-    else
-        hipLaunchKernelGGL(edge_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask);
-    SMI_HIP_CHECK(hipGetLastError());
-    if (tok >= 0) SMI_TRY(prof_end(tok, s));
-    return SMI_SUCCESS;
-}
-
-int launch_edge(const SweepArgs &a, int side_mask, hipStream_t s) { return launch_edge_res(a, side_mask, nullptr, s); }
-
-int launch_edge_src(const SweepArgs &a, int side_mask, const float *src, unsigned int *resid, hipStream_t s) {
-    if (!src) return launch_edge_res(a, side_mask, resid, s);
-    const long cells = 2L * a.cols + 2L * a.rows;
-    const int blocks = (int)((cells + 255) / 256);
-    int tok = -1;
-    if (prof_enabled()) SMI_TRY(prof_begin(SMI_PROF_STENCIL_EDGE, s, &tok));
-    if (resid)
-        hipLaunchKernelGGL(edge_src_res_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask, src, resid);
-    else
-        hipLaunchKernelGGL(edge_src_kernel, dim3(blocks), dim3(256), 0, s, a, side_mask, src);
-    SMI_HIP_CHECK(hipGetLastError());
+    switch (v.kind()) {
+    case Kind::Plain: SMI_TRY(launch_kernel(edge_kernel, grid, 0, s, nullptr, nullptr, a, side_mask)); break;
+    case Kind::Res: SMI_TRY(launch_kernel(edge_res_kernel, grid, 0, s, nullptr, nullptr, a, side_mask, v.resid)); break;
+    case Kind::Src: SMI_TRY(launch_kernel(edge_src_kernel, grid, 0, s, nullptr, nullptr, a, side_mask, v.src)); break;
+    case Kind::SrcRes:
+        SMI_TRY(launch_kernel(edge_src_res_kernel, grid, 0, s, nullptr, nullptr, a, side_mask, v.src, v.resid));
+        break;
+    }
     if (tok >= 0) SMI_TRY(prof_end(tok, s));
     return SMI_SUCCESS;
 }
@@ -492,7 +457,7 @@ int smi_stencil_step(const float *in, float *out, int x_local, int y_local, cons
                      SMI_Stream stream) {
     SweepArgs a;
     SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
-    return launch_sweep(a, (hipStream_t)stream);
+    return launch_sweep(a, Variant{}, (hipStream_t)stream);
 }
 
 int smi_stencil_step_residual(const float *in, float *out, int x_local, int y_local, const int mode[4],
@@ -501,7 +466,7 @@ int smi_stencil_step_residual(const float *in, float *out, int x_local, int y_lo
     SweepArgs a;
     SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
     SMI_ARG_CHECK(resid_bits && ((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
-    return launch_sweep_res(a, resid_bits, (hipStream_t)stream);
+    return launch_sweep(a, Variant{resid_bits}, (hipStream_t)stream);
 }
 
 int smi_stencil_step_source(const float *in, float *out, const float *src, int x_local, int y_local,
@@ -511,7 +476,7 @@ int smi_stencil_step_source(const float *in, float *out, const float *src, int x
     SMI_TRY(step_args(in, out, x_local, y_local, mode, halo, send_left, send_right, &a));
     SMI_TRY(check_src(src, in, out, x_local, y_local));
     SMI_ARG_CHECK(((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
-    return launch_sweep_src(a, src, resid_bits, (hipStream_t)stream);
+    return launch_sweep(a, Variant{resid_bits, src}, (hipStream_t)stream);
 }
 
 }  // extern "C"

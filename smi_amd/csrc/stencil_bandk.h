@@ -688,83 +688,38 @@ static_assert(4 * BandL<SWEEPD_MAX>::NPOS * BandL<SWEEPD_MAX>::PST * 8 <= kBandL
 static_assert(kBandLeanLds > 80 * 1024 && kBandLeanLds <= 160 * 1024, "one lean workgroup per CU");
 
 template <int K>
-int bandl_launch_impl(const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+int bandl_launch(const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     // (once per process, thread-safe: the reservation exceeds the 64 KiB a
     // launch may request without it)
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&bandl_kernel<K>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kBandLeanLds);
     SMI_HIP_CHECK(attr);
-    if (start || stop)
-        hipExtLaunchKernelGGL((bandl_kernel<K>), dim3(blocks), dim3(256), kBandLeanLds, s, start, stop, 0, a);
-    else
-        hipLaunchKernelGGL((bandl_kernel<K>), dim3(blocks), dim3(256), kBandLeanLds, s, a);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
+    return launch_kernel(bandl_kernel<K>, dim3(blocks), kBandLeanLds, s, start, stop, a);
 }
 
-template <int K>
-int bandk_launch_impl(const BandKArgs &a, int waves, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    if (start || stop)  // events carried by the dispatch itself (no marker packets around it)
-        hipExtLaunchKernelGGL((bandk_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, start, stop, 0, a);
+template <int K, Kind KD>
+int bandk_launch(const BandKArgs &a, int waves, const Variant &v, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    static_assert(variant_k(Family::Band, KD).has(K), "no such band instantiation");
+    const dim3 grid((waves + 3) / 4);
+    if constexpr (KD == Kind::Res)
+        return launch_kernel(bandk_res_kernel<K>, grid, 0, s, start, stop, a, v.resid);
+    else if constexpr (KD == Kind::Src)
+        return launch_kernel(bandk_src_kernel<K>, grid, 0, s, start, stop, a, *v.g_halo, v.src);
     else
-        hipLaunchKernelGGL((bandk_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, a);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
-}
-
-template <int K>
-int bandk_res_launch_impl(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s, hipEvent_t start,
-                          hipEvent_t stop) {
-    if (start || stop)
-        hipExtLaunchKernelGGL((bandk_res_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, start, stop, 0, a, resid);
-    else
-        hipLaunchKernelGGL((bandk_res_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, a, resid);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
-}
-
-template <int K>
-int bandk_src_launch_impl(const BandKArgs &a, const HaloK &gh, const float *src, int waves, hipStream_t s,
-                          hipEvent_t start, hipEvent_t stop) {
-    if (start || stop)
-        hipExtLaunchKernelGGL((bandk_src_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, start, stop, 0, a, gh, src);
-    else
-        hipLaunchKernelGGL((bandk_src_kernel<K>), dim3((waves + 3) / 4), dim3(256), 0, s, a, gh, src);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
+        return launch_kernel(bandk_kernel<K>, grid, 0, s, start, stop, a);
 }
 
 }  // namespace smi
 
-// The source instantiations, one unit per K (bandk_k<K>_src.hip).
-#define SMI_BANDK_SRC_INSTANCE(K)                                                                        \
-    namespace smi {                                                                                      \
-    int bandk_src_launch_k##K(const BandKArgs &a, const HaloK &gh, const float *src, int waves,          \
-                              hipStream_t s, hipEvent_t start, hipEvent_t stop) {                        \
-        return bandk_src_launch_impl<K>(a, gh, src, waves, s, start, stop);                              \
-    }                                                                                                    \
+// One translation unit per K and kind (bandk_k<K>.hip, bandk_k<K>_res.hip,
+// bandk_k<K>_src.hip); the lean kernel's beside the plain one of its K.
+#define SMI_BANDK_INSTANCE(K, KIND)                                                                       \
+    namespace smi {                                                                                       \
+    template int bandk_launch<K, Kind::KIND>(const BandKArgs &, int, const Variant &, hipStream_t, hipEvent_t, \
+                                             hipEvent_t);                                                 \
     }
 
-#define SMI_BANDK_RES_INSTANCE(K)                                                                       \
-    namespace smi {                                                                                      \
-    int bandk_res_launch_k##K(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s,         \
-                              hipEvent_t start, hipEvent_t stop) {                                       \
-        return bandk_res_launch_impl<K>(a, waves, resid, s, start, stop);                                \
-    }                                                                                                    \
-    }
-
-#define SMI_BANDK_INSTANCE(K)                                                                            \
-    namespace smi {                                                                                      \
-    int bandk_launch_k##K(const BandKArgs &a, int waves, hipStream_t s, hipEvent_t start,                \
-                          hipEvent_t stop) {                                                             \
-        return bandk_launch_impl<K>(a, waves, s, start, stop);                                           \
-    }                                                                                                    \
-    }
-
-#define SMI_BANDL_INSTANCE(K)                                                                            \
-    namespace smi {                                                                                      \
-    int bandl_launch_k##K(const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start,               \
-                          hipEvent_t stop) {                                                             \
-        return bandl_launch_impl<K>(a, blocks, s, start, stop);                                          \
-    }                                                                                                    \
+#define SMI_BANDL_INSTANCE(K)                                                                             \
+    namespace smi {                                                                                       \
+    template int bandl_launch<K>(const BandKArgs &, int, hipStream_t, hipEvent_t, hipEvent_t);            \
     }

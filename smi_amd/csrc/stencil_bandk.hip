@@ -4,40 +4,27 @@
 #include <cstdlib>
 
 #include "stencil_common.h"
-#include "stencil_src.h"
 
 namespace smi {
 
-#define SMI_BANDK_DECL(K) \
-    int bandk_launch_k##K(const BandKArgs &a, int waves, hipStream_t s, hipEvent_t start, hipEvent_t stop);
-SMI_FOR_K_3_12(SMI_BANDK_DECL)
-SMI_FOR_K_13_20(SMI_BANDK_DECL)
-#define SMI_BANDL_DECL(K) \
-    int bandl_launch_k##K(const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start, hipEvent_t stop);
-SMI_FOR_K_13_20(SMI_BANDL_DECL)
-// [K - SWEEPK_MIN] / [K - SWEEPD_MIN]; plan_bands refuses a K outside 3..20
-#define SMI_BANDK_ENTRY(K) bandk_launch_k##K,
-#define SMI_BANDL_ENTRY(K) bandl_launch_k##K,
-static constexpr decltype(bandk_launch_k3) *kBandK[] = {SMI_FOR_K_3_12(SMI_BANDK_ENTRY)
-                                                        SMI_FOR_K_13_20(SMI_BANDK_ENTRY)};
-static constexpr decltype(bandl_launch_k13) *kBandL[] = {SMI_FOR_K_13_20(SMI_BANDL_ENTRY)};
-// the residual instantiations (bandk_k<K>_res.hip), [K - SWEEPK_MIN]
-#define SMI_BANDK_RES_DECL(K)                                                                    \
-    int bandk_res_launch_k##K(const BandKArgs &a, int waves, unsigned int *resid, hipStream_t s, \
-                              hipEvent_t start, hipEvent_t stop);
-SMI_FOR_K_3_12(SMI_BANDK_RES_DECL)
-#define SMI_BANDK_RES_ENTRY(K) bandk_res_launch_k##K,
-static constexpr decltype(bandk_res_launch_k3) *kBandKRes[] = {SMI_FOR_K_3_12(SMI_BANDK_RES_ENTRY)};
-
-// the source instantiations (bandk_k<K>_src.hip), [K - SWEEPK_MIN], K = 3 .. SWEEPK_SRC_MAX
-#define SMI_BANDK_SRC_DECL(K)                                                                       \
-    int bandk_src_launch_k##K(const BandKArgs &a, const HaloK &gh, const float *src, int waves,     \
-                              hipStream_t s, hipEvent_t start, hipEvent_t stop);
-SMI_FOR_K_SRC(SMI_BANDK_SRC_DECL)
-#define SMI_BANDK_SRC_ENTRY(K) bandk_src_launch_k##K,
-static constexpr decltype(bandk_src_launch_k3) *kBandKSrc[] = {SMI_FOR_K_SRC(SMI_BANDK_SRC_ENTRY)};
-static_assert(sizeof(kBandKSrc) / sizeof(kBandKSrc[0]) == SWEEPK_SRC_MAX - SWEEPK_MIN + 1,
-              "SMI_FOR_K_SRC lists K = 3 .. SWEEPK_SRC_MAX");
+// [K - SWEEPK_MIN][kind]; nullptr where the kind has no instantiation at K.
+// The lean kernel (plain only): [K - SWEEPD_MIN].
+using BandKLaunch = decltype(bandk_launch<SWEEPK_MIN, Kind::Plain>);
+template <int K, Kind KD>
+constexpr BandKLaunch *bandk_entry() {
+    if constexpr (variant_k(Family::Band, KD).has(K))
+        return bandk_launch<K, KD>;
+    else
+        return nullptr;
+}
+#define SMI_BANDK_ROW(K) \
+    {bandk_entry<K, Kind::Plain>(), bandk_entry<K, Kind::Res>(), bandk_entry<K, Kind::Src>()},
+#define SMI_BANDL_ENTRY(K) bandl_launch<K>,
+static constexpr BandKLaunch *kBandK[][3] = {SMI_FOR_K_3_12(SMI_BANDK_ROW) SMI_FOR_K_13_20(SMI_BANDK_ROW)};
+static constexpr decltype(bandl_launch<SWEEPD_MIN>) *kBandL[] = {SMI_FOR_K_13_20(SMI_BANDL_ENTRY)};
+static_assert(sizeof(kBandK) / sizeof(kBandK[0]) == SWEEPD_MAX - SWEEPK_MIN + 1, "kBandK lists K = 3 .. SWEEPD_MAX");
+static_assert(sizeof(kBandL) / sizeof(kBandL[0]) == SWEEPD_MAX - SWEEPD_MIN + 1, "kBandL lists K = 13 .. SWEEPD_MAX");
+static_assert(variant_k(Family::Band, Kind::SrcRes).hi < SWEEPK_MIN, "a fourth kind needs a fourth column");
 
 static int compute_units() {
     static int cached[64] = {};
@@ -55,7 +42,7 @@ int plan_bands(int K, BandKArgs *ap, bool lean) {
     BandKArgs &a = *ap;
     const int X = a.rows, Y = a.cols;
     a.kc = kc_of(K);
-    SMI_ARG_CHECK(K >= SWEEPK_MIN && K <= SWEEPD_MAX, "bandk: K must be 3..20");
+    SMI_ARG_CHECK(variant_k(Family::Band, Kind::Plain).has(K), "bandk: K must be 3..20");
     SMI_ARG_CHECK(X >= 2 * K && Y >= 2 * a.kc && Y % 4 == 0, "bandk: tile smaller than 2K x 2KC");
     // one wave per 64 - 2K cells along a band (stencil_bandk.h)
     // lean kernel: two cells per lane, pair-aligned windows (BandL::SW)
@@ -91,9 +78,13 @@ int plan_bands(int K, BandKArgs *ap, bool lean) {
     return SMI_SUCCESS;
 }
 
-int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t stop, unsigned int *resid) {
-    SMI_ARG_CHECK(!resid || K <= SWEEPK_MAX, "bandk: the residual pass runs K <= 12");
-    const bool lean = K >= SWEEPD_MIN && g_tune.band_lean;
+int launch_bandk(int K, BandKArgs a, const Variant &v, int max_waves, hipStream_t s, hipEvent_t stop) {
+    const Kind kind = v.kind();
+    SMI_ARG_CHECK(kind != Kind::SrcRes && (!v.src || v.g_halo), "bandk: the source pass takes g's halos and no residual");
+    SMI_ARG_CHECK(kind != Kind::Res || K <= variant_k(Family::Band, kind).hi, "bandk: the residual pass runs K <= 12");
+    SMI_ARG_CHECK(kind != Kind::Src || variant_k(Family::Band, kind).has(K),
+                  "bandk: the source pass runs K = 3.." + std::to_string(variant_k(Family::Band, kind).hi));
+    const bool lean = variant_k(Family::BandLean, kind).has(K) && g_tune.band_lean;
     SMI_TRY(plan_bands(K, &a, lean));
     const int segs = a.first[4];
     if (segs == 0) {
@@ -118,37 +109,9 @@ int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t st
         int blocks = std::min(cus, (segs + 3) / 4);
         if (max_waves > 0) blocks = std::min(blocks, std::max(1, max_waves / 4));
         SMI_TRY(kBandL[K - SWEEPD_MIN](a, blocks, s, start, kstop));
-    } else if (resid) {
-        SMI_TRY(kBandKRes[K - SWEEPK_MIN](a, n, resid, s, start, kstop));
     } else {
-        SMI_TRY(kBandK[K - SWEEPK_MIN](a, n, s, start, kstop));
+        SMI_TRY(kBandK[K - SWEEPK_MIN][(int)kind](a, n, v, s, start, kstop));
     }
-    if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
-    return SMI_SUCCESS;
-}
-
-// The bands of a source pass (bandk_src_kernel): launch_bandk's one wave per
-// segment or max_waves looping waves, timed the same way under its own
-// profiling entry.  There is no lean and no residual variant.
-int launch_bandk_src(int K, BandKArgs a, const HaloK &g_halo, const float *src, int max_waves, hipStream_t s,
-                     hipEvent_t stop) {
-    SMI_ARG_CHECK(src, "bandk: NULL source");
-    SMI_ARG_CHECK(K >= SWEEPK_MIN && K <= SWEEPK_SRC_MAX,
-                  "bandk: the source pass runs K = 3.." + std::to_string(SWEEPK_SRC_MAX));
-    SMI_TRY(plan_bands(K, &a, false));
-    const int segs = a.first[4];
-    if (segs == 0) {
-        if (stop) SMI_HIP_CHECK(hipEventRecord(stop, s));
-        return SMI_SUCCESS;
-    }
-    const int n = max_waves > 0 ? std::min(segs, std::max(4, max_waves)) : segs;
-    hipEvent_t start = nullptr, kstop = stop, after = nullptr;
-    int tok = -1;
-    if (prof_enabled()) {
-        SMI_TRY(prof_launch(SMI_PROF_STENCIL_EDGE, &tok, K, 0.0, &start, &kstop));
-        after = stop;
-    }
-    SMI_TRY(kBandKSrc[K - SWEEPK_MIN](a, g_halo, src, n, s, start, kstop));
     if (after) SMI_HIP_CHECK(hipEventRecord(after, s));
     return SMI_SUCCESS;
 }

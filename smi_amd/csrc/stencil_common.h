@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include <hip/hip_ext.h>
+
 #include "smi_internal.h"
 
 namespace smi {
@@ -102,17 +104,89 @@ struct Tuning {
     int band_lean = 1;
     int host_join = 1;  // smi_stencil_set_join
     int solve_fused = 0;  // smi_stencil_set_solve_check: 1 = smi_stencil_solve checks with a fused K-step pass
+    int source_bands = 0;  // smi_stencil_set_source_bands: 1 = multi-rank source runs take K-step passes (0: single steps)
 };
 extern Tuning g_tune;
+
+// The variant axis.  What a step or pass carries besides the state, every
+// field nullable; kind() is the one name a variant has on the host: it picks
+// the kernel of a family (the tables of stencilk.hip / stencil_bandk.hip, the
+// ladder of stencil.hip), and variant_k() below says at which K it exists.
+//   resid   the kernels also max-accumulate the bit pattern of |out - in| (a
+//           K-step pass: |v_K - v_{K-1}|) over the cells they store into
+//           *resid, one filtered atomic per wave (stencil_resid_dev.h)
+//   src     the update with a source term, out = 0.25f * ((((S + W) + E) + N)
+//           + g): this rank's tile of g, read at the cell's own address
+//   g_halo  g's depth-K staging, laid out like the state's (the band kernels
+//           of a multi-rank source pass; received once per K-phase)
+struct HaloK;
+enum class Kind { Plain = 0, Res = 1, Src = 2, SrcRes = 3 };
+struct Variant {
+    unsigned int *resid = nullptr;
+    const float *src = nullptr;
+    const HaloK *g_halo = nullptr;
+    Kind kind() const { return Kind((resid ? 1 : 0) | (src ? 2 : 0)); }
+};
+
+// Steps per pass of the kernel families: the K-step sweep (stencilk.h), the
+// deep sweep (stencild.h) and the band kernels (stencil_bandk.h).  The source
+// sweep exists for K = 3 .. SWEEPK_SRC_MAX: the deepest pass (<= 12) whose
+// kernel compiles for gfx950 with no scratch and two waves per SIMD (DESIGN.md
+// section 5 has the register count of every K).
+constexpr int SWEEPK_MIN = 3, SWEEPK_MAX = 12, SWEEPK_SRC_MAX = 9;
+constexpr int SWEEPD_MIN = 13, SWEEPD_MAX = 20;
+// The K of the per-K instantiation units (stencilk_k / stencild_k / bandk_k
+// <K>.hip): the host sides build their dispatch tables, indexed by K - first,
+// from these two lists.
+#define SMI_FOR_K_3_12(X) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
+#define SMI_FOR_K_13_20(X) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
+
+// Which K a kind supports in a family (lo > hi: the family has no such
+// variant).  The argument checks, the planners, smi_stencil_source_max_depth
+// and the dispatch tables' entries all come from here; a unit file exists for
+// exactly these (family, kind, K).
+enum class Family { Sweep, Band, BandLean };
+struct KRange {
+    int lo, hi;
+    constexpr bool has(int K) const { return K >= lo && K <= hi; }
+};
+constexpr KRange variant_k(Family f, Kind k) {
+    const bool plain = k == Kind::Plain, res = k == Kind::Res, src = k == Kind::Src;
+    switch (f) {
+    case Family::Sweep: return {SWEEPK_MIN, plain || res ? SWEEPK_MAX : src ? SWEEPK_SRC_MAX : 0};
+    case Family::Band: return {SWEEPK_MIN, plain ? SWEEPD_MAX : res ? SWEEPK_MAX : src ? SWEEPK_SRC_MAX : 0};
+    case Family::BandLean: return {SWEEPD_MIN, plain ? SWEEPD_MAX : 0};
+    }
+    return {1, 0};
+}
+
+// One launch of workgroups of 256: timed by the dispatch itself when an event
+// is carried (start / stop recorded by the launch's own packet, no marker
+// packets around it), an ordinary launch otherwise.
+template <class... P, class... A>
+int launch_kernel(void (*kernel)(P...), dim3 grid, unsigned int lds, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                  A... args) {
+    if (start || stop)
+        hipExtLaunchKernelGGL(kernel, grid, dim3(256), lds, s, start, stop, 0, static_cast<P>(args)...);
+    else
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, static_cast<P>(args)...);
+    SMI_HIP_CHECK(hipGetLastError());
+    return SMI_SUCCESS;
+}
+// Resident waves of `kernel` (workgroups of 256, no dynamic LDS) on the
+// current device: one round of a grid.  cache: the caller's per-device memo
+// for this kernel.  0 when a query fails.
+int resident_waves(const void *kernel, int (&cache)[64]);
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 int check_tile(const float *in, const float *out, int rows, int cols);
 // a source array of the tile's shape: non-NULL, 16-byte aligned, overlapping neither buffer
 int check_src(const float *src, const float *buf0, const float *buf1, int rows, int cols);
 
-// single step (stencil.hip)
-int launch_sweep(const SweepArgs &a, hipStream_t s);
-int launch_edge(const SweepArgs &a, int side_mask, hipStream_t s);
+// single step (stencil.hip): the sweep over a tile, and the cells of its
+// halo-facing sides (side_mask); v: plain, residual, source, source + residual
+int launch_sweep(const SweepArgs &a, const Variant &v, hipStream_t s);
+int launch_edge(const SweepArgs &a, int side_mask, const Variant &v, hipStream_t s);
 int launch_pack_cols(const float *in, int rows, int cols, float *left, float *right, hipStream_t s);
 
 // two steps per pass (stencil2.hip).  skip[k] = 1: the 2-wide ring on side k
@@ -146,12 +220,6 @@ struct SweepKArgs {
     int row_lo, row_hi, col_lo, col_hi;
     int gT, gB, gL, gR;
 };
-constexpr int SWEEPK_MIN = 3, SWEEPK_MAX = 12;
-// The K of the per-K instantiation units (stencilk_k / stencild_k / bandk_k
-// <K>.hip): the host sides declare the units' entry points and build their
-// dispatch tables, indexed by K - first, from these two lists.
-#define SMI_FOR_K_3_12(X) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
-#define SMI_FOR_K_13_20(X) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
 // a sweep's output rectangle: float4-aligned columns, inside the tile
 inline int check_sweep_rect(const char *who, const SweepKArgs &a) {
     SMI_ARG_CHECK(a.cols % 4 == 0 && a.col_lo % 4 == 0 && a.col_hi % 4 == 0,
@@ -164,11 +232,21 @@ inline int check_sweep_rect(const char *who, const SweepKArgs &a) {
 // as many columns, >= K): 4 for K >= 9 (224 stored columns, line-aligned
 // stores), else the minimal ceil(K / 4).
 __host__ __device__ constexpr int sweepk_apron_lanes(int K) { return K >= 9 ? 4 : (K + 3) / 4; }
-int launch_sweepk(int K, const SweepKArgs &a, hipStream_t s);
-// src (nullable; K <= SWEEPK_SRC_MAX of stencil_src.h, no resid): the source instantiation
-int launch_sweepk_ex(int K, const SweepKArgs &a, int ht, int reserve, bool prof, hipStream_t s,
-                     hipEvent_t stop = nullptr, unsigned int *resid = nullptr, const float *src = nullptr);
+// One pass (K > SWEEPK_MAX: the deep sweep below).  v: plain, residual or
+// source, at the K of variant_k(Family::Sweep, .); reserve: wave slots left to
+// the comm stream's kernels (smi_stencil_set_bands); stop (nullable): an event
+// the launch's dispatch records when the kernel completes.
+int launch_sweepk(int K, const SweepKArgs &a, const Variant &v, int reserve, hipStream_t s,
+                  hipEvent_t stop = nullptr);
 int sweepk_window_cols(int K);  // output columns per 256-column window
+// the per-K units' entry points (stencilk.h; explicitly instantiated by
+// SMI_SWEEPK_INSTANCE): the launch of ceil(nstrips * nrb / 4) workgroups, and
+// the kernel's resident waves
+template <int K, Kind KD>
+int sweepk_launch(const SweepKArgs &a, int nstrips, int nrb, const Variant &v, hipStream_t s, hipEvent_t start,
+                  hipEvent_t stop);
+template <int K, Kind KD>
+int sweepk_resident();
 
 // Deep K-step sweep (stencild.h / stencild.hip, SWEEPD_MIN <= K <= SWEEPD_MAX):
 // same arguments and output as the K-step sweep (a whole single tile, or a
@@ -180,7 +258,6 @@ int sweepk_window_cols(int K);  // output columns per 256-column window
 // with a global bottom edge (it walks upwards: one extra DPP move per W/E
 // pair) shortened to weight wlast/16 of a block -- so that every wave of the
 // single round finishes at about the same time.
-constexpr int SWEEPD_MIN = 13, SWEEPD_MAX = 20;
 struct SweepDGeom {
     int nstrips;   // all strips
     int n_int;     // interior strips (no global-edge column): [int0, int0 + n_int)
@@ -204,6 +281,11 @@ bool sweepd_fits(int K, const SweepKArgs &a);
 int sweepd_window_cols(int K);
 int sweepd_geometry(int K, const SweepKArgs &a, int reserve, SweepDGeom *g);
 int launch_sweepd(int K, const SweepKArgs &a, int reserve, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+// the per-K units' entry points (stencild.h, SMI_SWEEPD_INSTANCE)
+template <int K>
+int sweepd_launch(const SweepKArgs &a, const SweepDGeom &g, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+template <int K>
+int sweepd_resident();
 
 // Depth-K halos (stencil_bandk.h / stencil_bandk.hip).  KC = 4 ceil(K/4):
 // the column depth, whole float4 groups.  Receive side: top = rows -K..-1 and
@@ -236,11 +318,17 @@ struct BandKArgs {
 };
 int plan_bands(int K, BandKArgs *a, bool lean);  // fills kc, first[], sw, rlo, rhi
 // the bands of a pass: one wave per segment, or max_waves (> 0) waves;
-// stop (nullable): an event the launch's dispatch records at completion;
-// resid (nullable, K <= 12): the residual instantiation, which also
-// max-accumulates |v_K - v_{K-1}| of the band cells into *resid
-int launch_bandk(int K, BandKArgs a, int max_waves, hipStream_t s, hipEvent_t stop = nullptr,
-                 unsigned int *resid = nullptr);
+// v: plain, residual or source (src and g_halo both set), at the K of
+// variant_k(Family::Band, .) -- the lean kernel (K >= SWEEPD_MIN under
+// smi_stencil_set_band_kernel(1)) is plain only; stop (nullable): an event the
+// launch's dispatch records at completion
+int launch_bandk(int K, BandKArgs a, const Variant &v, int max_waves, hipStream_t s, hipEvent_t stop = nullptr);
+// the per-K units' entry points (stencil_bandk.h, SMI_BANDK_INSTANCE /
+// SMI_BANDL_INSTANCE): ceil(waves / 4) workgroups; `blocks` lean workgroups
+template <int K, Kind KD>
+int bandk_launch(const BandKArgs &a, int waves, const Variant &v, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+template <int K>
+int bandl_launch(const BandKArgs &a, int blocks, hipStream_t s, hipEvent_t start, hipEvent_t stop);
 int launch_packk(const float *in, int rows, int cols, int K, const HaloK &h, hipStream_t s);
 
 }  // namespace smi

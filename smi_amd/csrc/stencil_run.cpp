@@ -11,8 +11,6 @@
 #include <cstdlib>
 
 #include "stencil_common.h"
-#include "stencil_resid.h"
-#include "stencil_src.h"
 
 namespace smi {
 
@@ -134,8 +132,10 @@ struct Tile {
     int rows, cols;
     Neighbours nb;
     int side_mask;        // bit 0..3: neighbour on side top, bottom, left, right
-    unsigned int *resid;  // the residual word while the final phase of a residual run is enqueued, else nullptr
-    const float *src;     // this rank's tile of the source term (a source run), else nullptr
+    // src: this rank's tile of the source term (a source run); resid: the
+    // residual word while the final phase of a residual run is enqueued;
+    // g_halo: set by a K-phase of a source run
+    Variant v;
     int cur;              // index of the buffer holding the current state
     const float *in() const { return buf[cur]; }
     float *out() const { return buf[cur ^ 1]; }
@@ -357,9 +357,22 @@ static int tile_fuse(int rows, int cols, bool multi) {
     return K;
 }
 
+// K-step passes for `rest` steps under the balanced-remainder rule above;
+// returns the steps left to shallower phases (0, 1 or 2 -- or all of them
+// when rest < K and cannot be one pass of its own)
+static int add_k_passes(Plan &p, int K, int rest) {
+    const int passes = rest / K + 1, base = rest / passes, extra = rest % passes;
+    if (rest % K >= SWEEPK_MIN && base >= SWEEPK_MIN) {
+        p.add(base + 1, extra);
+        p.add(base, passes - extra);
+        return 0;
+    }
+    p.add(K, rest / K);
+    return rest % K;
+}
+
 static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
     Plan p;
-    auto add = [&](int k, int n) { p.add(k, n); };
     const int fuse = g_tune.fuse;
     int K = tile_fuse(rows, cols, multi);
     if (K > SWEEPK_MAX) {
@@ -369,23 +382,12 @@ static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
         if (!sweepd_fits(K, interior_rect(rows, cols, K, multi ? 1 | 2 : 0))) K = SWEEPK_MAX;
     }
     if (cols < 8 || K < SWEEPK_MIN) K = 0;
-    int rest = timesteps;
-    if (K) {
-        const int passes = rest / K + 1, base = rest / passes, extra = rest % passes;
-        if (rest % K >= SWEEPK_MIN && base >= SWEEPK_MIN) {
-            add(base + 1, extra);
-            add(base, passes - extra);
-            rest = 0;
-        } else {
-            add(K, rest / K);
-            rest %= K;
-        }
-    }
+    int rest = K ? add_k_passes(p, K, timesteps) : timesteps;
     if (fuse >= 2 && rows >= 4 && cols >= 8) {
-        add(2, rest / 2);
+        p.add(2, rest / 2);
         rest %= 2;
     }
-    add(1, rest);
+    p.add(1, rest);
     return p;
 }
 
@@ -400,17 +402,13 @@ static Plan make_plan(int rows, int cols, int timesteps, bool multi) {
 // is its own last phase; make_plan yields at most 3 phases (two balanced
 // depths, or K + pair + single), so 4 still hold every schedule.
 static Plan make_plan_residual(int rows, int cols, int timesteps, bool multi) {
-    int kr = std::min(std::min(tile_fuse(rows, cols, multi), SWEEPK_MAX), timesteps);
+    int kr = std::min(std::min(tile_fuse(rows, cols, multi), variant_k(Family::Sweep, Kind::Res).hi), timesteps);
     if (cols < 8 || kr < SWEEPK_MIN) kr = 1;
     Plan p = make_plan(rows, cols, timesteps - kr, multi);
     p.add(kr, 1);
     p.resid_last = true;
     return p;
 }
-
-// smi_stencil_set_source_bands: 1 = multi-rank source runs take K-step passes
-// (0: single steps)
-static int g_source_bands = 0;
 
 // A source run (smi_stencil_run_source; stencilk.h "Source instantiations").
 // One tile with cols >= 8: passes of min(steps per pass, SWEEPK_SRC_MAX) steps
@@ -426,24 +424,24 @@ static int g_source_bands = 0;
 static Plan make_plan_source(int rows, int cols, int timesteps, bool multi, bool resid) {
     Plan p;
     int K = 0;
-    if (cols >= 8 && !resid && (!multi || g_source_bands))
-        K = std::min(multi ? tile_fuse(rows, cols, true) : g_tune.fuse, SWEEPK_SRC_MAX);
-    if (K < SWEEPK_MIN) K = 0;
-    int rest = timesteps;
-    if (K) {
-        const int passes = rest / K + 1, base = rest / passes, extra = rest % passes;
-        if (rest % K >= SWEEPK_MIN && base >= SWEEPK_MIN) {
-            p.add(base + 1, extra);
-            p.add(base, passes - extra);
-            rest = 0;
-        } else {
-            p.add(K, rest / K);
-            rest %= K;
-        }
-    }
-    p.add(1, rest);
+    if (cols >= 8 && !resid && (!multi || g_tune.source_bands))
+        K = std::min(multi ? tile_fuse(rows, cols, true) : g_tune.fuse, variant_k(Family::Sweep, Kind::Src).hi);
+    p.add(1, K >= SWEEPK_MIN ? add_k_passes(p, K, timesteps) : timesteps);
     p.resid_last = resid;
     return p;
+}
+static_assert(variant_k(Family::Band, Kind::Src).hi == variant_k(Family::Sweep, Kind::Src).hi &&
+                  variant_k(Family::Band, Kind::Res).hi == variant_k(Family::Sweep, Kind::Res).hi,
+              "the planners take a K-step pass's depth from the sweep; its bands run the same K");
+
+// The schedule of a run of `kind`: smi_stencil_run (Plain), smi_stencil_run_residual
+// (Res), a source run (Src) or the checked source step (SrcRes).
+static Plan plan_for(Kind kind, int rows, int cols, int timesteps, bool multi) {
+    switch (kind) {
+    case Kind::Plain: return make_plan(rows, cols, timesteps, multi);
+    case Kind::Res: return make_plan_residual(rows, cols, timesteps, multi);
+    default: return make_plan_source(rows, cols, timesteps, multi, kind == Kind::SrcRes);
+    }
 }
 
 // single-step / pair arguments (halo views and buffers set by the phases)
@@ -468,13 +466,13 @@ static int run_single(Tile &t, const Plan &plan, unsigned int *resid, hipStream_
     Sweep2Args a2 = pair_args(t);
     for (int ph = 0; ph < plan.nph; ++ph) {
         const int K = plan.k[ph];
-        t.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
+        t.v.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
         SweepKArgs ak = interior_rect(t.rows, t.cols, K, 0);
         for (int p = 0; p < plan.n[ph]; ++p, t.cur ^= 1) {
             if (K >= SWEEPK_MIN) {
                 ak.in = t.in();
                 ak.out = t.out();
-                SMI_TRY(launch_sweepk_ex(K, ak, 0, 0, true, s, nullptr, t.resid, t.src));
+                SMI_TRY(launch_sweepk(K, ak, t.v, 0, s));
             } else if (K == 2) {
                 a2.in = t.in();
                 a2.out = t.out();
@@ -482,7 +480,7 @@ static int run_single(Tile &t, const Plan &plan, unsigned int *resid, hipStream_
             } else {
                 a.in = t.in();
                 a.out = t.out();
-                SMI_TRY(launch_sweep_src(a, t.src, t.resid, s));
+                SMI_TRY(launch_sweep(a, t.v, s));
             }
         }
     }
@@ -576,7 +574,7 @@ struct PassSched {
 };
 
 // ---- K steps per pass (depth-K halos)
-// t.src (a source run): the source instantiations of both kernels, and g's own
+// t.v.src (a source run): the source instantiations of both kernels, and g's own
 // depth-K halos in gk -- a second staging, exchanged here once for the phase
 // (g is constant over a run, but the phases differ in depth; nothing is kept
 // across calls: the caller may change src between runs).
@@ -588,22 +586,21 @@ static int k_passes(Tile &t, PassSched &sc, int K, int npass, const HaloK &hk, c
     for (int k = 0; k < 4; ++k) bk.has[k] = t.has(k);
     bk.pack = t.side_mask != 0;
     bk.h = hk;
-    // t.resid: the residual pass -- both kernels' residual instantiations, one word
-    auto ring = [&](hipStream_t st, hipEvent_t stop) {
-        if (t.src) return launch_bandk_src(K, bk, gk, t.src, g_tune.band_reserve, st, stop);
-        return launch_bandk(K, bk, g_tune.band_reserve, st, stop, t.resid);
-    };
+    // t.v.resid: the residual pass -- both kernels' residual instantiations, one word
+    Variant v = t.v;
+    if (v.src) v.g_halo = &gk;
+    auto ring = [&](hipStream_t st, hipEvent_t stop) { return launch_bandk(K, bk, v, g_tune.band_reserve, st, stop); };
     auto interior = [&](hipStream_t st, hipEvent_t stop) {
-        return launch_sweepk_ex(K, ak, 0, g_tune.band_reserve, true, st, stop, t.resid, t.src);
+        return launch_sweepk(K, ak, v, g_tune.band_reserve, st, stop);
     };
     auto xchgk = [&](const float *tile, hipStream_t st) { return exchange(t.c, msgsk(t, tile, K, hk), true, st); };
     SMI_TRY(launch_packk(t.in(), t.rows, t.cols, K, hk, sc.cs));
     SMI_TRY(xchgk(t.in(), sc.cs));
-    if (t.src) {
+    if (v.src) {
         // g's halos, directly behind the state's on the comm stream: every
         // rank posts the two exchanges in this order
-        SMI_TRY(launch_packk(t.src, t.rows, t.cols, K, gk, sc.cs));
-        SMI_TRY(exchange(t.c, msgsk(t, t.src, K, gk), true, sc.cs));
+        SMI_TRY(launch_packk(v.src, t.rows, t.cols, K, gk, sc.cs));
+        SMI_TRY(exchange(t.c, msgsk(t, v.src, K, gk), true, sc.cs));
     }
     sc.kpass = 0;
     for (int p = 0; p < npass; ++p, t.cur ^= 1) {
@@ -649,12 +646,12 @@ static int single_steps(Tile &t, PassSched &sc, int npass, const Halo2 &h2) {
     for (int k = 0; k < 4; ++k)
         if (inner.mode[k] == SMI_SIDE_HALO) inner.mode[k] = SMI_SIDE_SKIP;
     inner.send_left = inner.send_right = nullptr;
-    // (t.src: the source kernels, each rank reading its own tile of src)
-    auto edge = [&](hipStream_t st, hipEvent_t) { return launch_edge_src(a, t.side_mask, t.src, t.resid, st); };
-    auto interior = [&](hipStream_t st, hipEvent_t) { return launch_sweep_src(inner, t.src, t.resid, st); };
+    // (t.v.src: the source kernels, each rank reading its own tile of src)
+    auto edge = [&](hipStream_t st, hipEvent_t) { return launch_edge(a, t.side_mask, t.v, st); };
+    auto interior = [&](hipStream_t st, hipEvent_t) { return launch_sweep(inner, t.v, st); };
     // without overlap the full sweep reads the halos itself
     auto no_edge = [&](hipStream_t, hipEvent_t) { return (int)SMI_SUCCESS; };
-    auto full = [&](hipStream_t st, hipEvent_t) { return launch_sweep_src(a, t.src, t.resid, st); };
+    auto full = [&](hipStream_t st, hipEvent_t) { return launch_sweep(a, t.v, st); };
     auto xchg1 = [&](const float *tile, hipStream_t st) {
         const HaloMsgs x = side_msgs(t, tile, 1, 1, a.halo[0], a.halo[1], a.halo[2], a.halo[3], s_left, s_right);
         return exchange(t.c, x, false, st);
@@ -694,16 +691,16 @@ static int run_multi(Tile &t, const Plan &plan, unsigned int *resid, hipStream_t
     for (int i = 0; i < plan.nph; ++i) kmax = std::max(kmax, plan.k[i] >= SWEEPK_MIN ? plan.k[i] : 0);
     // a source run with a K-phase: g's depth-K staging behind the state's
     const size_t need2 = halo2_elems(t.rows, t.cols), needk = halok_elems(t.rows, t.cols, kmax);
-    SMI_TRY(ensure_halo(c, need2 + needk + (t.src ? needk : 0)));
+    SMI_TRY(ensure_halo(c, need2 + needk + (t.v.src ? needk : 0)));
     const Halo2 h2 = halo2_layout(c->halo, t.rows, t.cols);
 
     for (int ph = 0; ph < plan.nph; ++ph) {
         const int K = plan.k[ph], npass = plan.n[ph];
-        t.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
+        t.v.resid = plan.resid_last && ph == plan.nph - 1 ? resid : nullptr;
         SMI_TRY(sc.phase_start());
         if (K >= SWEEPK_MIN)
             SMI_TRY(k_passes(t, sc, K, npass, halok_layout(c->halo + need2, t.rows, t.cols, kmax),
-                             halok_layout(c->halo + need2 + (t.src ? needk : 0), t.rows, t.cols, kmax)));
+                             halok_layout(c->halo + need2 + (t.v.src ? needk : 0), t.rows, t.cols, kmax)));
         else if (K == 2)
             SMI_TRY(pair_passes(t, sc, npass, h2));
         else
@@ -738,17 +735,19 @@ static int find_comm(SMI_Comm comm, Comm **c) {
 // schedule of make_plan_residual, whose last pass's kernels also
 // max-accumulate |x_T - x_{T-1}| into *resid (timesteps >= 1; one step is the
 // checked step of smi_stencil_solve: a single residual step, stencil.hip).
-// src (nullable): a source run, the schedule of make_plan_source; with resid
-// it is the one checked step of smi_stencil_solve_source.
+// v.src: a source run, the schedule of make_plan_source; with v.resid it is the
+// one checked step of smi_stencil_solve_source.
 static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local, int px, int py, int timesteps,
-                     SMI_Stream stream_, int *result_index, unsigned int *resid, const float *src = nullptr) {
+                     SMI_Stream stream_, int *result_index, const Variant &v) {
+    unsigned int *const resid = v.resid;
+    const float *const src = v.src;
     SMI_TRY(check_grid(c, buf0, buf1, x_local, y_local, px, py));
     if (src) SMI_TRY(check_src(src, buf0, buf1, x_local, y_local));
     SMI_ARG_CHECK(!(src && resid) || timesteps == 1, "a source run takes its residual from one single step");
     SMI_ARG_CHECK(timesteps >= 0, "timesteps < 0");
     SMI_ARG_CHECK(result_index, "NULL result_index");
     SMI_ARG_CHECK(!resid || timesteps >= 1, "a residual run takes at least one step");
-    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, nullptr, src, 0};
+    Tile t{c, {buf0, buf1}, x_local, y_local, neighbours_of(c->rank, px, py), 0, Variant{nullptr, src}, 0};
 #ifdef SMI_LOOPBACK_REHEARSAL
     // Timing-rehearsal build only (never the product library; built by
     // `smi_amd/build.py --rehearsal`, driven by tools/rehearsal.py): with
@@ -766,9 +765,7 @@ static int run_steps(Comm *c, float *buf0, float *buf1, int x_local, int y_local
         if (side_nb[k] >= 0) t.side_mask |= 1 << k;
 
     const bool multi = t.side_mask != 0;
-    const Plan plan = src     ? make_plan_source(t.rows, t.cols, timesteps, multi, resid != nullptr)
-                      : resid ? make_plan_residual(t.rows, t.cols, timesteps, multi)
-                              : make_plan(t.rows, t.cols, timesteps, multi);
+    const Plan plan = plan_for(v.kind(), t.rows, t.cols, timesteps, multi);
     *result_index = plan.passes() & 1;
     prof_break_chain();  // markers chain only between this run's own passes
     if (timesteps == 0) return SMI_SUCCESS;
@@ -885,20 +882,16 @@ int smi_stencil_deep_geometry(int rows, int cols, int K, int side_mask, int *wav
     return SMI_SUCCESS;
 }
 
-enum class PlanKind { Run, Residual, Source };
-
-static int plan_query(PlanKind kind, int x_local, int y_local, int px, int py, int rank, int timesteps,
+static int plan_query(Kind kind, int x_local, int y_local, int px, int py, int rank, int timesteps,
                       SMI_StencilPhase *phases, int max_phases, int *nphases, int *neighbours, int *result_index) {
     SMI_ARG_CHECK(x_local >= 1 && y_local >= 4 && y_local % 4 == 0, "tile must be >= 1 x 4, y_local % 4 == 0");
     SMI_ARG_CHECK(px >= 1 && py >= 1 && rank >= 0 && rank < px * py, "rank outside the px x py grid");
-    const bool residual = kind == PlanKind::Residual;
+    const bool residual = kind == Kind::Res;
     SMI_ARG_CHECK(timesteps >= (residual ? 1 : 0), residual ? "a residual run takes at least one step" : "timesteps < 0");
     SMI_ARG_CHECK(nphases && (phases || max_phases == 0), "NULL output");
     const Neighbours nb = neighbours_of(rank, px, py);
     const bool multi = nb.top >= 0 || nb.bottom >= 0 || nb.left >= 0 || nb.right >= 0;
-    const Plan p = kind == PlanKind::Source ? make_plan_source(x_local, y_local, timesteps, multi, false)
-                   : residual               ? make_plan_residual(x_local, y_local, timesteps, multi)
-                                            : make_plan(x_local, y_local, timesteps, multi);
+    const Plan p = plan_for(kind, x_local, y_local, timesteps, multi);
     SMI_ARG_CHECK(max_phases >= p.nph, "max_phases too small (4 always suffice)");
     for (int i = 0; i < p.nph; ++i) {
         phases[i].steps_per_pass = p.k[i];
@@ -915,26 +908,26 @@ static int plan_query(PlanKind kind, int x_local, int y_local, int px, int py, i
 
 int smi_stencil_plan(int x_local, int y_local, int px, int py, int rank, int timesteps, SMI_StencilPhase *phases,
                      int max_phases, int *nphases, int *neighbours, int *result_index) {
-    return plan_query(PlanKind::Run, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases,
+    return plan_query(Kind::Plain, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases,
                       neighbours, result_index);
 }
 
 int smi_stencil_plan_source(int x_local, int y_local, int px, int py, int rank, int timesteps, SMI_StencilPhase *phases,
                             int max_phases, int *nphases, int *neighbours, int *result_index) {
-    return plan_query(PlanKind::Source, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases,
+    return plan_query(Kind::Src, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases,
                       neighbours, result_index);
 }
 
 int smi_stencil_source_max_depth(int *k) {
     SMI_ARG_CHECK(k, "NULL output");
-    *k = SWEEPK_SRC_MAX;
+    *k = variant_k(Family::Sweep, Kind::Src).hi;
     return SMI_SUCCESS;
 }
 
 int smi_stencil_plan_residual(int x_local, int y_local, int px, int py, int rank, int timesteps,
                               SMI_StencilPhase *phases, int max_phases, int *nphases, int *neighbours,
                               int *result_index) {
-    return plan_query(PlanKind::Residual, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
+    return plan_query(Kind::Res, x_local, y_local, px, py, rank, timesteps, phases, max_phases, nphases, neighbours,
                       result_index);
 }
 
@@ -951,12 +944,12 @@ int smi_stencil_get_solve_check(int *fused) {
 
 int smi_stencil_set_source_bands(int fused) {
     SMI_ARG_CHECK(fused <= 1, "source bands: 0 (multi-rank source runs take single steps) or 1 (K-step passes)");
-    if (fused >= 0) g_source_bands = fused;
+    if (fused >= 0) g_tune.source_bands = fused;
     return SMI_SUCCESS;
 }
 
 int smi_stencil_get_source_bands(int *fused) {
-    if (fused) *fused = g_source_bands;
+    if (fused) *fused = g_tune.source_bands;
     return SMI_SUCCESS;
 }
 
@@ -966,14 +959,14 @@ int smi_stencil_run_residual(SMI_Comm comm, float *buf0, float *buf1, int x_loca
     SMI_TRY(find_comm(comm, &c));
     SMI_ARG_CHECK(timesteps >= 1, "a residual run takes at least one step");
     SMI_ARG_CHECK(resid_bits && ((uintptr_t)resid_bits & 3u) == 0, "resid_bits must be a 4-byte aligned device word");
-    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, resid_bits);
+    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, Variant{resid_bits});
 }
 
 int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local, int y_local, int px, int py,
                     int timesteps, SMI_Stream stream_, int *result_index) {
     Comm *c = nullptr;
     SMI_TRY(find_comm(comm, &c));
-    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, nullptr);
+    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, Variant{});
 }
 
 int smi_stencil_run_source(SMI_Comm comm, float *buf0, float *buf1, const float *src, int x_local, int y_local, int px,
@@ -982,7 +975,7 @@ int smi_stencil_run_source(SMI_Comm comm, float *buf0, float *buf1, const float 
     SMI_TRY(check_src(src, buf0, buf1, x_local, y_local));
     Comm *c = nullptr;
     SMI_TRY(find_comm(comm, &c));
-    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, nullptr, src);
+    return run_steps(c, buf0, buf1, x_local, y_local, px, py, timesteps, stream_, result_index, Variant{nullptr, src});
 }
 
 // smi_stencil_solve (src == nullptr) and smi_stencil_solve_source: the same
@@ -1012,17 +1005,17 @@ static int solve_steps(SMI_Comm comm, float *buf0, float *buf1, const float *src
             // smi_stencil_set_solve_check(1): the steps up to the check point
             // as one residual run, whose last K-step pass carries the residual
             SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
-            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done, stream_, &idx, local));
+            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done, stream_, &idx, Variant{local}));
             cur ^= idx;
         } else {
             // the unchecked steps, exactly as smi_stencil_run plans that many
             SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, next - done - 1, stream_, &idx,
-                              nullptr, src));
+                              Variant{nullptr, src}));
             cur ^= idx;
             // the checked step; its kernels run on this communicator's streams,
             // all ordered after `stream` here and joined back to it at the end
             SMI_HIP_CHECK(hipMemsetAsync(local, 0, sizeof(unsigned int), s));
-            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, local, src));
+            SMI_TRY(run_steps(c, buf[cur], buf[cur ^ 1], x_local, y_local, px, py, 1, stream_, &idx, Variant{local, src}));
             cur ^= idx;
         }
         done = next;

@@ -454,31 +454,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_DEEP_WP
     }
 }
 
+template <int K>
+int sweepd_launch(const SweepKArgs &a, const SweepDGeom &g, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    return launch_kernel(sweepd_kernel<K>, dim3((g.tasks + 3) / 4), 0, s, start, stop, a, g);
+}
+
+template <int K>
+int sweepd_resident() {
+    static int cache[64] = {};
+    return resident_waves(reinterpret_cast<const void *>(sweepd_kernel<K>), cache);
+}
+
 }  // namespace smi
 
 // One translation unit per K (stencild_k<K>.hip): the eight instantiations
 // compile in parallel.
-#define SMI_SWEEPD_INSTANCE(K)                                                                           \
-    namespace smi {                                                                                      \
-    int sweepd_launch_k##K(const SweepKArgs &a, const SweepDGeom &g, int blocks, hipStream_t s,          \
-                           hipEvent_t start, hipEvent_t stop) {                                          \
-        if (start || stop)                                                                               \
-            hipExtLaunchKernelGGL((sweepd_kernel<K>), dim3(blocks), dim3(256), 0, s, start, stop, 0, a, g); \
-        else                                                                                             \
-            hipLaunchKernelGGL((sweepd_kernel<K>), dim3(blocks), dim3(256), 0, s, a, g);                  \
-        SMI_HIP_CHECK(hipGetLastError());                                                                \
-        return SMI_SUCCESS;                                                                              \
-    }                                                                                                    \
-    int sweepd_resident_k##K() {                                                                         \
-        static int cached[64] = {};                                                                      \
-        int dev = 0;                                                                                     \
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;                          \
-        if (cached[dev]) return cached[dev];                                                             \
-        int per_cu = 0, cus = 0;                                                                         \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweepd_kernel<K>, 256, 0) != hipSuccess) \
-            return 0;                                                                                    \
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0; \
-        cached[dev] = per_cu * cus * 4;                                                                  \
-        return cached[dev];                                                                              \
-    }                                                                                                    \
+#define SMI_SWEEPD_INSTANCE(K)                                                                                  \
+    namespace smi {                                                                                             \
+    template int sweepd_launch<K>(const SweepKArgs &, const SweepDGeom &, hipStream_t, hipEvent_t, hipEvent_t); \
+    template int sweepd_resident<K>();                                                                          \
     }

@@ -4,15 +4,10 @@
 
 namespace smi {
 
-#define SMI_SWEEPD_DECL(K)                                                                            \
-    int sweepd_launch_k##K(const SweepKArgs &a, const SweepDGeom &g, int blocks, hipStream_t s,          \
-                           hipEvent_t start, hipEvent_t stop);                                        \
-    int sweepd_resident_k##K();
-SMI_FOR_K_13_20(SMI_SWEEPD_DECL)
-#define SMI_SWEEPD_ENTRY(K) {sweepd_launch_k##K, sweepd_resident_k##K},
+#define SMI_SWEEPD_ENTRY(K) {sweepd_launch<K>, sweepd_resident<K>},
 static constexpr struct {
-    decltype(sweepd_launch_k13) *launch;
-    decltype(sweepd_resident_k13) *resident;
+    decltype(sweepd_launch<SWEEPD_MIN>) *launch;
+    decltype(sweepd_resident<SWEEPD_MIN>) *resident;
 } kSweepD[] = {SMI_FOR_K_13_20(SMI_SWEEPD_ENTRY)};  // [K - SWEEPD_MIN]
 
 int sweepd_window_cols(int K) { return 256 - 8 * ((K + 3) / 4); }
@@ -87,7 +82,7 @@ int launch_sweepd(int K, const SweepKArgs &a, int reserve, hipStream_t s, hipEve
     SMI_TRY(check_sweep_rect("sweepd", a));
     SweepDGeom g;
     SMI_TRY(sweepd_geometry(K, a, reserve, &g));  // also refuses a K outside kSweepD
-    return kSweepD[K - SWEEPD_MIN].launch(a, g, (g.tasks + 3) / 4, s, start, stop);
+    return kSweepD[K - SWEEPD_MIN].launch(a, g, s, start, stop);
 }
 
 }  // namespace smi

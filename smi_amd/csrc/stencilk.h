@@ -89,7 +89,7 @@
 // out itself (`stl` and the row's in_block below).
 //
 // Source instantiations (SRC; sweepk_src_kernel<K>, one translation unit per K
-// in stencilk_k<K>_src.hip, K = 3 .. SWEEPK_SRC_MAX of stencil_src.h).  Every
+// in stencilk_k<K>_src.hip, K = 3 .. SWEEPK_SRC_MAX of stencil_common.h).  Every
 // level adds one operand per cell, out = 0.25 * ((((S + W) + E) + N) + g),
 // g the cell of a second array `src` that travels as a kernel argument of its
 // own (SweepKArgs and the plain kernels' code stay as they are).  Level l at
@@ -192,7 +192,7 @@ enum { ROW_NONE = 0, ROW_TOP = 1, ROW_BOT = 2, ROW_FULL = 3, ROW_UP = 4 };
 // SMI_SWEEPK_ALT): row block rb walks down for even rb and up for odd rb, so
 // the 2K apron rows two neighbouring blocks share are read by both at the
 // same time (the ends of both walks, or the starts of both) and the second
-// read hits L2.  Needs an even number of row blocks (launch_sweepk_ex).
+// read hits L2.  Needs an even number of row blocks (launch_sweepk).
 __host__ __device__ constexpr bool walks_up(int row) { return row == ROW_BOT || row == ROW_UP; }
 
 template <int K, int U, bool RES = false, bool SRC = false>
@@ -630,110 +630,41 @@ __global__ __launch_bounds__(256) SMI_SWEEPK_SRC_WPE_ATTR void sweepk_src_kernel
     sweepk_task<K, false, true>(a, strip, rb, nrb, lane, nullptr, src);
 }
 
-template <int K>
-int sweepk_src_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, const float *src, hipStream_t s,
-                           hipEvent_t start, hipEvent_t stop) {
-    if (start || stop)
-        hipExtLaunchKernelGGL((sweepk_src_kernel<K>), dim3(blocks), dim3(256), 0, s, start, stop, 0, a, nstrips, nrb,
-                              src);
+// the kernel of a kind and the arguments it takes besides (a, nstrips, nrb)
+template <int K, Kind KD, class F>
+auto sweepk_with_kernel(const Variant &v, F &&f) {
+    static_assert(variant_k(Family::Sweep, KD).has(K), "no such sweep instantiation");
+    if constexpr (KD == Kind::Res)
+        return f(sweepk_res_kernel<K>, v.resid);
+    else if constexpr (KD == Kind::Src)
+        return f(sweepk_src_kernel<K>, v.src);
     else
-        hipLaunchKernelGGL((sweepk_src_kernel<K>), dim3(blocks), dim3(256), 0, s, a, nstrips, nrb, src);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
+        return f(sweepk_kernel<K>);
 }
 
-template <int K>
-int sweepk_src_resident_impl() {
-    static int cached[64] = {};  // per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (cached[dev]) return cached[dev];
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweepk_src_kernel<K>, 256, 0) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    cached[dev] = per_cu * cus * 4;
-    return cached[dev];
+template <int K, Kind KD>
+int sweepk_launch(const SweepKArgs &a, int nstrips, int nrb, const Variant &v, hipStream_t s, hipEvent_t start,
+                  hipEvent_t stop) {
+    const dim3 grid((unsigned int)(((long)nstrips * nrb + 3) / 4));
+    return sweepk_with_kernel<K, KD>(v, [&](auto kernel, auto... extra) {
+        return launch_kernel(kernel, grid, 0, s, start, stop, a, nstrips, nrb, extra...);
+    });
 }
 
-template <int K>
-int sweepk_res_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, unsigned int *resid, hipStream_t s,
-                           hipEvent_t start, hipEvent_t stop) {
-    if (start || stop)
-        hipExtLaunchKernelGGL((sweepk_res_kernel<K>), dim3(blocks), dim3(256), 0, s, start, stop, 0, a, nstrips, nrb,
-                              resid);
-    else
-        hipLaunchKernelGGL((sweepk_res_kernel<K>), dim3(blocks), dim3(256), 0, s, a, nstrips, nrb, resid);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
-}
-
-template <int K>
-int sweepk_res_resident_impl() {
-    static int cached[64] = {};  // per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (cached[dev]) return cached[dev];
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweepk_res_kernel<K>, 256, 0) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    cached[dev] = per_cu * cus * 4;
-    return cached[dev];
-}
-
-template <int K>
-int sweepk_launch_impl(const SweepKArgs &a, int nstrips, int nrb, int blocks, hipStream_t s, hipEvent_t start,
-                       hipEvent_t stop) {
-    if (start || stop)  // events carried by the dispatch itself (no marker packets around it)
-        hipExtLaunchKernelGGL((sweepk_kernel<K>), dim3(blocks), dim3(256), 0, s, start, stop, 0, a, nstrips, nrb);
-    else
-        hipLaunchKernelGGL((sweepk_kernel<K>), dim3(blocks), dim3(256), 0, s, a, nstrips, nrb);
-    SMI_HIP_CHECK(hipGetLastError());
-    return SMI_SUCCESS;
-}
-
-// resident waves of sweepk<K> on the current device (one round of the grid)
-template <int K>
-int sweepk_resident_impl() {
-    static int cached[64] = {};  // per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (cached[dev]) return cached[dev];
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweepk_kernel<K>, 256, 0) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    cached[dev] = per_cu * cus * 4;
-    return cached[dev];
+template <int K, Kind KD>
+int sweepk_resident() {
+    static int cache[64] = {};
+    return sweepk_with_kernel<K, KD>(
+        Variant{}, [](auto kernel, auto...) { return resident_waves(reinterpret_cast<const void *>(kernel), cache); });
 }
 
 }  // namespace smi
 
-// One translation unit per K (stencilk_k<K>.hip) so the ten instantiations
-// compile in parallel.
-#define SMI_SWEEPK_INSTANCE(K)                                                                           \
+// One translation unit per K and kind (stencilk_k<K>.hip, stencilk_k<K>_res.hip,
+// stencilk_k<K>_src.hip) so the instantiations compile in parallel.
+#define SMI_SWEEPK_INSTANCE(K, KIND)                                                                     \
     namespace smi {                                                                                      \
-    int sweepk_launch_k##K(const SweepKArgs &a, int nstrips, int nrb, int blocks, hipStream_t s,         \
-                           hipEvent_t start, hipEvent_t stop) {                                          \
-        return sweepk_launch_impl<K>(a, nstrips, nrb, blocks, s, start, stop);                           \
-    }                                                                                                    \
-    int sweepk_resident_k##K() { return sweepk_resident_impl<K>(); }                                     \
-    }
-
-// The residual instantiations, one unit per K as well (stencilk_k<K>_res.hip).
-#define SMI_SWEEPK_RES_INSTANCE(K)                                                                       \
-    namespace smi {                                                                                      \
-    int sweepk_res_launch_k##K(const SweepKArgs &a, int nstrips, int nrb, int blocks, unsigned int *r,   \
-                               hipStream_t s, hipEvent_t start, hipEvent_t stop) {                       \
-        return sweepk_res_launch_impl<K>(a, nstrips, nrb, blocks, r, s, start, stop);                    \
-    }                                                                                                    \
-    int sweepk_res_resident_k##K() { return sweepk_res_resident_impl<K>(); }                             \
-    }
-
-// The source instantiations, one unit per K as well (stencilk_k<K>_src.hip).
-#define SMI_SWEEPK_SRC_INSTANCE(K)                                                                       \
-    namespace smi {                                                                                      \
-    int sweepk_src_launch_k##K(const SweepKArgs &a, int nstrips, int nrb, int blocks, const float *src,  \
-                               hipStream_t s, hipEvent_t start, hipEvent_t stop) {                       \
-        return sweepk_src_launch_impl<K>(a, nstrips, nrb, blocks, src, s, start, stop);                  \
-    }                                                                                                    \
-    int sweepk_src_resident_k##K() { return sweepk_src_resident_impl<K>(); }                             \
+    template int sweepk_launch<K, Kind::KIND>(const SweepKArgs &, int, int, const Variant &, hipStream_t, \
+                                              hipEvent_t, hipEvent_t);                                   \
+    template int sweepk_resident<K, Kind::KIND>();                                                       \
     }

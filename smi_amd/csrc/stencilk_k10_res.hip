@@ -1,3 +1,3 @@
 // stencilk_k10_res.hip -- sweepk_res_kernel<10>, the residual instantiation (stencilk.h)
 #include "stencilk.h"
-SMI_SWEEPK_RES_INSTANCE(10)
+SMI_SWEEPK_INSTANCE(10, Res)

@@ -1,3 +1,3 @@
 // stencilk_k3.hip -- sweepk_kernel<3> (stencilk.h)
 #include "stencilk.h"
-SMI_SWEEPK_INSTANCE(3)
+SMI_SWEEPK_INSTANCE(3, Plain)

@@ -1,3 +1,3 @@
 // stencilk_k6.hip -- sweepk_kernel<6> (stencilk.h)
 #include "stencilk.h"
-SMI_SWEEPK_INSTANCE(6)
+SMI_SWEEPK_INSTANCE(6, Plain)

@@ -1,3 +1,3 @@
 // stencilk_k6_res.hip -- sweepk_res_kernel<6>, the residual instantiation (stencilk.h)
 #include "stencilk.h"
-SMI_SWEEPK_RES_INSTANCE(6)
+SMI_SWEEPK_INSTANCE(6, Res)

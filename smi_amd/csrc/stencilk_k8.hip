@@ -1,3 +1,3 @@
 // stencilk_k8.hip -- sweepk_kernel<8> (stencilk.h)
 #include "stencilk.h"
-SMI_SWEEPK_INSTANCE(8)
+SMI_SWEEPK_INSTANCE(8, Plain)

@@ -1,3 +1,3 @@
 // stencilk_k9_src.hip -- sweepk_src_kernel<9>, the source instantiation (stencilk.h)
 #include "stencilk.h"
-SMI_SWEEPK_SRC_INSTANCE(9)
+SMI_SWEEPK_INSTANCE(9, Src)
