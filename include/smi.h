@@ -21,6 +21,7 @@
 #include "smi/pop.h"
 #include "smi/stencil.h"
 #include "smi/reduce.h"
+#include "smi/allreduce.h"
 #include "smi/bcast.h"
 #include "smi/scatter.h"
 #include "smi/gather.h"

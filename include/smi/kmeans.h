@@ -62,6 +62,29 @@ int smi_kmeans_accumulate(const float *points, int n, int dims, const int *assig
 int smi_kmeans(SMI_Comm comm, const float *points, int n_local, int dims, int clusters, int width,
                float *centroids, int iterations, SMI_Stream stream);
 
+/* The cross-rank half of ComputeMeans in one kernel: row r of `sums`
+ * (clusters*dims floats, row pitch `ld_sums` elements) and row r of `counts`
+ * (clusters ints, row pitch `ld_counts` elements) are rank r's contribution,
+ * 1 <= nranks <= 64.  centroids[k][d] = fold(sums column) /
+ * (float)fold(counts column): both folds are the rank-order SMI_ADD fold of
+ * reduce.h (4 slots for the floats, 1 for the ints, which wrap), the division
+ * is IEEE.  An empty cluster gives 0/0 = NaN; a -0 sum becomes +0 through the
+ * fold's +0 start.  The bits are those of smi_reduce_fold on the sums, on the
+ * counts, and the divide of smi_kmeans. */
+int smi_kmeans_means(const float *sums, const int *counts, int nranks, size_t ld_sums,
+                     size_t ld_counts, int clusters, int dims, float *centroids, SMI_Stream stream);
+
+/* How smi_kmeans brings the sums and counts of all ranks together.
+ * 0 (default): the reference's four collectives (reduce and bcast of the
+ * sums, of the counts) and a divide.  1: one transfer group per iteration --
+ * every rank sends its record (sums and counts, adjacent) to every other
+ * rank -- and one smi_kmeans_means launch over the n records; a record above
+ * 256 KiB takes two smi_allreduce calls and the divide instead.  The
+ * centroids are bit-identical in both modes, on every rank.  fused = -1
+ * keeps the setting.  Process-wide; the same value on every rank. */
+int smi_kmeans_set_means(int fused);
+int smi_kmeans_get_means(int *fused);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,7 +90,7 @@ int smi_stencil_run(SMI_Comm comm, float *buf0, float *buf1, int x_local,
  * no extra pass, no extra exchange and no host synchronisation beyond the
  * run's own.  The residual is rank-local: the function does no reduce (a
  * caller with its own convergence loop reduces the words of its ranks as it
- * sees fit; smi_stencil_solve does so with smi_reduce + smi_bcast).  The word
+ * sees fit; smi_stencil_solve does so with an integer-max smi_allreduce).  The word
  * is complete when the work enqueued on `stream` has finished.
  * Schedule (smi_stencil_plan_residual): the last launch is one pass of
  * K_r = min(steps_per_pass, 12, timesteps) steps, K_r clipped like every
@@ -117,7 +117,7 @@ int smi_stencil_run_residual(SMI_Comm comm, float *buf0, float *buf1, int x_loca
  * check points run as smi_stencil_run runs that many steps (same plan under
  * the current fusion setting), step t_j itself is one single step with the
  * residual fused into its kernels.  The local bit pattern then goes through
- * an integer-max smi_reduce to rank 0 and an smi_bcast, so every rank sees
+ * one integer-max smi_allreduce (include/smi/allreduce.h), so every rank sees
  * the same r_t and stops at the same step: the first check point with
  * r_t <= tol (a NaN never satisfies it), or max_steps -- which still returns
  * SMI_SUCCESS, with *converged = 0.

@@ -78,6 +78,7 @@ SIGNATURES = {
     "smi_stencil_get_deep": (I, [ctypes.POINTER(I)] * 3),
     "smi_reduce": (I, [SMI_Comm, P, P, SZ, I, I, I, I, P]),
     "smi_reduce_fold": (I, [P, P, I, SZ, SZ, I, I, P]),
+    "smi_allreduce": (I, [SMI_Comm, P, P, SZ, I, I, I, P]),
     "smi_bcast": (I, [SMI_Comm, P, SZ, I, I, I, P]),
     "smi_set_pipeline_bytes": (I, [SZ]),
     "smi_get_pipeline_bytes": (I, [ctypes.POINTER(SZ)]),
@@ -91,6 +92,9 @@ SIGNATURES = {
     "smi_kmeans_assign": (I, [P, I, I, P, I, I, P, P]),
     "smi_kmeans_accumulate": (I, [P, I, I, P, I, P, P, P]),
     "smi_kmeans": (I, [SMI_Comm, P, I, I, I, I, P, I, P]),
+    "smi_kmeans_means": (I, [P, P, I, SZ, SZ, I, I, P, P]),
+    "smi_kmeans_set_means": (I, [I]),
+    "smi_kmeans_get_means": (I, [ctypes.POINTER(I)]),
     "smi_prof_enable": (I, [I]),
     "smi_prof_reset": (I, []),
     "smi_prof_read": (I, [I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),

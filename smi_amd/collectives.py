@@ -44,6 +44,20 @@ def reduce(comm: Comm, send: torch.Tensor, recv: torch.Tensor | None, op="add", 
               root, port, _lib.stream_handle(stream))
 
 
+def allreduce(comm: Comm, send: torch.Tensor, recv: torch.Tensor | None = None, op="add", port: int = 0,
+              stream=None) -> torch.Tensor:
+    """Element-wise reduce of every rank's `send` into every rank's `recv`
+    (smi_allreduce: the bits of `reduce` on its root, on all ranks).
+    recv=None reduces in place, into `send`; the result tensor is returned."""
+    if recv is None:
+        recv = send
+    elif recv.dtype != send.dtype or recv.numel() != send.numel():
+        raise _lib.SMIError("allreduce: recv must have send's dtype and element count")
+    _lib.call("smi_allreduce", comm.handle, send.data_ptr(), recv.data_ptr(), send.numel(), _smi_type(send),
+              _op(op), port, _lib.stream_handle(stream))
+    return recv
+
+
 def bcast(comm: Comm, buf: torch.Tensor, root: int = 0, port: int = 0, stream=None) -> None:
     """Root's `buf` copied into every rank's `buf` (bcast.cl)."""
     _lib.call("smi_bcast", comm.handle, buf.data_ptr(), buf.numel(), _smi_type(buf), root, port,

@@ -385,6 +385,160 @@ int smi_reduce(SMI_Comm comm, const void *sendbuf, void *recvbuf, size_t count, 
     return SMI_SUCCESS;
 }
 
+// smi_allreduce: the fold of smi_reduce on every rank (include/smi/allreduce.h).
+//
+// Workspace ordering.  Every use of the communicator's workspace is ordered
+// through comm_stream.  The pipelined path stages into it from groups on
+// comm_stream, and comm_stream waits (ev_f) for each fold that reads it.  The
+// small path stages and folds on the caller's stream, bracketed by two
+// events: the caller's stream first waits for a record on comm_stream (ev_s:
+// behind every earlier group there, and behind every fold comm_stream was
+// made to wait for), and comm_stream then waits for the small path's fold
+// (ev_f).  Two calls on different streams are therefore ordered in issue
+// order, whichever path each takes.  (Running the small path's group and fold
+// on comm_stream instead orders them as well and measured the same,
+// DESIGN.md section 7; this form keeps a latency-bound call off a second
+// stream.)
+//
+// In place (sendbuf == recvbuf).  Small path: the group only reads sendbuf
+// (the receives land in staging rows), and group.end() returns with the
+// stream ordered after every peer's copy of it; the fold then loads all n
+// rows of a thread's elements before it stores them, and no other thread
+// reads those elements.  Pipelined path: F(i) rewrites piece i of my own
+// chunk, which only F(i) itself reads (same threads, loads before stores; no
+// X sends a rank's own chunk); AG(i) overwrites piece i of every foreign
+// chunk, which X(i) has sent before -- X(i) sits in an earlier group of the
+// same stream (group i-2, or one of the two opening groups) -- and which
+// nothing reads afterwards.
+int smi_allreduce(SMI_Comm comm, const void *sendbuf, void *recvbuf, size_t count, SMI_Datatype type,
+                  SMI_Op op, int port, SMI_Stream stream_) {
+    (void)port;  // as in smi_reduce
+    Comm *c = lookup_comm(comm);
+    if (!c) {
+        set_error("unknown communicator");
+        return SMI_ERR_BAD_COMM;
+    }
+    const int n = c->size, me = c->rank;
+    SMI_ARG_CHECK(n <= kMaxFoldRanks, "allreduce supports up to 64 ranks");
+    SMI_ARG_CHECK(op >= SMI_ADD && op <= SMI_MIN, "bad op");
+    const size_t esz = type_size(type);
+    if (esz == 0) {
+        set_error("unsupported data type");
+        return SMI_ERR_UNSUPPORTED;
+    }
+    if (count == 0) return SMI_SUCCESS;
+    SMI_ARG_CHECK(sendbuf, "NULL sendbuf");
+    SMI_ARG_CHECK(recvbuf, "NULL recvbuf");
+    const size_t bytes = count * esz;
+    {
+        const uintptr_t a = (uintptr_t)sendbuf, b = (uintptr_t)recvbuf;
+        SMI_ARG_CHECK(a == b || a + bytes <= b || b + bytes <= a,
+                      "sendbuf and recvbuf overlap (only sendbuf == recvbuf is allowed)");
+    }
+    hipStream_t s = (hipStream_t)stream_;
+
+    if (n == 1) {
+        FoldRows rows{};
+        rows.row[0] = sendbuf;
+        return launch_fold(rows, recvbuf, 1, count, type, op, s);
+    }
+    Transport *tp = c->transport.get();
+    hipStream_t cs_ = c->comm_stream;
+    hipEvent_t ev_s, ev_f, ev_x[3];
+    SMI_TRY(comm_event(c, 2, &ev_s));
+    SMI_TRY(comm_event(c, 3, &ev_f));
+    for (int k = 0; k < 3; ++k) SMI_TRY(comm_event(c, 4 + k, &ev_x[k]));
+    const char *sb = (const char *)sendbuf;
+    char *rb = (char *)recvbuf;
+
+    if (bytes <= kReduceFanInBytes) {
+        // Latency-bound: one round.  Every rank's whole buffer to every other
+        // rank, then the canonical rank-order fold of the n rows (my own row
+        // read from sendbuf) straight into recvbuf: the rows and the fold of
+        // smi_reduce's root, so its bits, on every rank.
+        const size_t rst = (bytes + 15) / 16 * 16;  // staging row stride (16-byte aligned rows)
+        void *ws = nullptr;
+        SMI_TRY(comm_workspace(c, (size_t)n * rst, &ws));
+        // after whatever comm_stream still does with the workspace (an earlier
+        // call's groups, and the folds it has been made to wait for)
+        SMI_HIP_CHECK(hipEventRecord(ev_s, cs_));
+        SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_s, 0));
+        FoldRows rows{};
+        {
+            Group grp(tp);
+            SMI_TRY(grp.begin(s));
+            for (int k = 0; k < n; ++k) {
+                char *row = (char *)ws + (size_t)k * rst;
+                rows.row[k] = k == me ? sendbuf : (const void *)row;
+                if (k == me) continue;
+                SMI_TRY(tp->send(sendbuf, bytes, k));
+                SMI_TRY(tp->recv(row, bytes, k));
+            }
+            SMI_TRY(grp.end());
+        }
+        SMI_TRY(launch_fold(rows, recvbuf, n, count, type, op, s));
+        // whatever comm_stream does next with the workspace comes after this fold
+        SMI_HIP_CHECK(hipEventRecord(ev_f, s));
+        SMI_HIP_CHECK(hipStreamWaitEvent(cs_, ev_f, 0));
+        return SMI_SUCCESS;
+    }
+
+    // smi_reduce's owner-chunk pipeline (chunks, pieces, the two staging slots
+    // and the X/F bridging as there), every rank a root of its own chunk:
+    //   comm stream: X(0), X(1), [wait F(0)] {AG(0) + X(2)}, [wait F(1)] {AG(1) + X(3)} ...
+    //   main stream: [wait X(i)] F(i)
+    // F(i) folds my piece i into recvbuf at my chunk's position; AG(i) sends
+    // it to every other rank and receives chunk k's piece i at chunk k's
+    // position.  No reduced-chunk buffer: recvbuf is one.
+    const size_t cs = chunk_elems(count, n, esz);
+    const Pieces pc = pieces_of(cs, esz);
+    constexpr size_t kStagePad = 4096;  // as in smi_reduce
+    const size_t pst = pc.ps + kStagePad / esz;
+    void *ws = nullptr;
+    SMI_TRY(comm_workspace(c, 2 * (size_t)n * pst * esz, &ws));
+    char *stage = (char *)ws;
+    auto slot = [&](int i, int k) { return stage + ((size_t)(i & 1) * n + k) * pst * esz; };
+    auto sub = [&](int owner, int i) { return sub_len(chunk_len(count, cs, owner), pc.ps, i); };
+    auto at = [&](int owner, int i) { return ((size_t)owner * cs + (size_t)i * pc.ps) * esz; };
+    SMI_HIP_CHECK(hipEventRecord(ev_s, s));
+    SMI_HIP_CHECK(hipStreamWaitEvent(cs_, ev_s, 0));
+    auto group = [&](int xi, int gi) -> int {  // {X(xi)} + {AG(gi)}, either may be -1
+        Group grp(tp);
+        SMI_TRY(grp.begin(cs_));
+        for (int k = 0; k < n; ++k) {
+            if (k == me) continue;
+            if (xi >= 0) {
+                SMI_TRY(tp->send(sb + at(k, xi), sub(k, xi) * esz, k));
+                SMI_TRY(tp->recv(slot(xi, k), sub(me, xi) * esz, k));
+            }
+            if (gi >= 0) {
+                SMI_TRY(tp->send(rb + at(me, gi), sub(me, gi) * esz, k));
+                SMI_TRY(tp->recv(rb + at(k, gi), sub(k, gi) * esz, k));
+            }
+        }
+        SMI_TRY(grp.end());
+        if (xi >= 0) SMI_HIP_CHECK(hipEventRecord(ev_x[xi % 3], cs_));
+        return SMI_SUCCESS;
+    };
+    SMI_TRY(group(0, -1));
+    if (pc.n > 1) SMI_TRY(group(1, -1));
+    for (int i = 0; i < pc.n; ++i) {
+        SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_x[i % 3], 0));
+        const size_t len = sub(me, i);
+        if (len) {
+            FoldRows rows{};
+            for (int k = 0; k < n; ++k) rows.row[k] = (k == me) ? (const void *)(sb + at(me, i)) : (const void *)slot(i, k);
+            SMI_TRY(launch_fold(rows, rb + at(me, i), n, len, type, op, s));
+        }
+        SMI_HIP_CHECK(hipEventRecord(ev_f, s));
+        SMI_HIP_CHECK(hipStreamWaitEvent(cs_, ev_f, 0));
+        SMI_TRY(group(i + 2 < pc.n ? i + 2 : -1, i));
+    }
+    SMI_HIP_CHECK(hipEventRecord(ev_s, cs_));  // the caller's stream owns the result
+    SMI_HIP_CHECK(hipStreamWaitEvent(s, ev_s, 0));
+    return SMI_SUCCESS;
+}
+
 int smi_bcast(SMI_Comm comm, void *buf, size_t count, SMI_Datatype type, int root, int port,
               SMI_Stream stream_) {
     (void)port;

@@ -28,7 +28,9 @@
 // chains skip those points; the oracle restates the literal form and the GPU
 // tests compare bitwise.
 #include <algorithm>
+#include <atomic>
 
+#include "fold.h"
 #include "smi_internal.h"
 
 namespace smi {
@@ -284,8 +286,103 @@ __global__ void divide_kernel(const float *__restrict__ sums, const int *__restr
     cen[i] = __fdiv_rn(sums[i], (float)counts[i / dims]);
 }
 
+// ComputeMeans across the ranks in one launch (smi_kmeans_means): what
+// collectives.hip's fold_kernel on the sums, the same on the counts, and
+// divide_kernel compute in three.  Row r of each table is rank r's
+// contribution; the rows may lie anywhere (a rank's own record where
+// launch_accumulate wrote it, the others in staging).
+constexpr int kMaxMeansRanks = 64;
+struct MeansRows {
+    const float *sums[kMaxMeansRanks];
+    const int *counts[kMaxMeansRanks];
+};
+
+// One thread per VEC consecutive centroid elements (VEC = 4: one 16-byte load
+// per row, all rows 16-byte aligned and dims a multiple of 4, so the four
+// share a cluster; VEC = 1: the scalar path for everything else).  Both folds
+// are fold.h's, in rank order: 4 rotating slots for the fp32 sums, 1 for the
+// counts.  Rows go in batches of 8 whose loads are all in flight before the
+// ordered fold consumes them, as in the reduce's fold kernel.
+template <int VEC>
+__global__ __launch_bounds__(256) void means_kernel(MeansRows rows, int n, size_t total, int dims,
+                                                    float *__restrict__ cen) {
+    using V4 = float __attribute__((ext_vector_type(4)));
+    constexpr int S = 4, KB = 8;
+    const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+    if (base >= total) return;
+    const size_t k = base / (size_t)dims;
+    float q[VEC][S];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e)
+#pragma unroll
+        for (int j = 0; j < S; ++j) q[e][j] = op_init<float, SMI_ADD>();
+    int cq = op_init<int, SMI_ADD>();
+    for (int k0 = 0; k0 < n; k0 += KB) {
+        float d[KB][VEC];
+        int cn[KB];
+#pragma unroll
+        for (int i = 0; i < KB; ++i) {
+            const int r = min(k0 + i, n - 1);  // past n: a valid row, never folded
+            if constexpr (VEC == 4)
+                *reinterpret_cast<V4 *>(&d[i][0]) = *reinterpret_cast<const V4 *>(rows.sums[r] + base);
+            else
+                d[i][0] = rows.sums[r][base];
+            cn[i] = rows.counts[r][k];
+        }
+#pragma unroll
+        for (int i = 0; i < KB; ++i) {
+            // a row past n leaves the slots as they are -- by selects, not by a
+            // branch: behind a branch the compiler sinks each row's loads to
+            // its fold and the batch becomes one memory round trip per row
+            const bool on = k0 + i < n;  // uniform
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float nv = op_apply<float, SMI_ADD>(d[i][e], q[e][0]);
+#pragma unroll
+                for (int j = 0; j < S - 1; ++j) q[e][j] = on ? q[e][j + 1] : q[e][j];
+                q[e][S - 1] = on ? nv : q[e][S - 1];
+            }
+            cq = on ? op_apply<int, SMI_ADD>(cn[i], cq) : cq;
+        }
+    }
+    const float cnt = (float)op_apply<int, SMI_ADD>(op_init<int, SMI_ADD>(), cq);
+    float res[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        float t = op_init<float, SMI_ADD>();
+#pragma unroll
+        for (int j = 0; j < S; ++j) t = op_apply<float, SMI_ADD>(t, q[e][j]);
+        res[e] = __fdiv_rn(t, cnt);  // kmeans_smi.cl:200, as divide_kernel
+    }
+    if constexpr (VEC == 4)
+        *reinterpret_cast<V4 *>(cen + base) = *reinterpret_cast<const V4 *>(res);
+    else
+        cen[base] = res[0];
+}
+
 // ---------------------------------------------------------------- host ----
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// smi_kmeans_set_means: 0 = the reference's four collectives and a divide,
+// 1 = one record exchange and one means_kernel launch per iteration
+static std::atomic<int> g_means_fused{0};
+// a record (sums + counts) above this takes two smi_allreduce calls instead:
+// smi_reduce's fan-in switch point (collectives.hip kReduceFanInBytes)
+constexpr size_t kMeansRecordBytes = (size_t)256 * 1024;
+
+static int launch_means(const MeansRows &rows, int n, int clusters, int dims, float *cen, hipStream_t s) {
+    const size_t total = (size_t)clusters * dims;
+    bool vec = dims % 4 == 0 && ((uintptr_t)cen & 15u) == 0;
+    for (int r = 0; r < n; ++r) vec = vec && ((uintptr_t)rows.sums[r] & 15u) == 0;
+    if (vec)
+        hipLaunchKernelGGL(means_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, rows, n, total,
+                           dims, cen);
+    else
+        hipLaunchKernelGGL(means_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows, n, total,
+                           dims, cen);
+    SMI_HIP_CHECK(hipGetLastError());
+    return SMI_SUCCESS;
+}
 
 struct KmeansWork {
     int *idx, *bcount, *list, *counts, *base;
@@ -368,6 +465,71 @@ static int launch_divide(const float *sums, const int *counts, float *cen, int c
     return SMI_SUCCESS;
 }
 
+// smi_kmeans under smi_kmeans_set_means(1).  A rank's record is its sums
+// followed by its counts (kd floats, clusters ints: one transfer); the
+// scratch holds one record slot per rank, and launch_accumulate writes this
+// rank's into slot `me`.  Per iteration: one transport group on the caller's
+// stream (my record to every rank, every rank's record into its slot), then
+// one means_kernel launch over the n slots -- smi_reduce's rows in smi_reduce's
+// order and divide_kernel's division, so mode 0's bits.  The scratch is this
+// call's own stream-ordered allocation: the communicator's workspace is not
+// used.
+static int kmeans_fused(Comm *c, SMI_Comm comm, const float *points, int n, int dims, int clusters, int width,
+                        float *centroids, int iterations, const KmeansWork &sz, hipStream_t s) {
+    const int nr = c->size, me = c->rank;
+    SMI_ARG_CHECK(nr <= kMaxMeansRanks, "kmeans means supports up to 64 ranks");
+    const size_t kd = (size_t)clusters * dims;
+    const size_t rec = kd * 4 + (size_t)clusters * 4;
+    const bool direct = nr == 1 || rec <= kMeansRecordBytes;
+    // direct: nr record slots; otherwise this rank's record and the reduced one
+    const size_t slot = up256(rec);
+    const size_t extra = (direct ? (size_t)nr : 2) * slot;
+    void *ws = nullptr;
+    SMI_HIP_CHECK(hipMallocAsync(&ws, sz.bytes + extra, s));
+    const KmeansWork w = kmeans_layout((char *)ws, n, dims, clusters);
+    char *recs = (char *)ws + sz.bytes;
+    auto rsums = [&](int r) { return (float *)(recs + (size_t)r * slot); };
+    auto rcounts = [&](int r) { return (int *)(recs + (size_t)r * slot + kd * 4); };
+    const int mine = direct ? me : 0;
+    MeansRows rows{};
+    for (int r = 0; r < (direct ? nr : 0); ++r) {
+        rows.sums[r] = rsums(r);
+        rows.counts[r] = rcounts(r);
+    }
+    Transport *tp = c->transport.get();
+    int rc = SMI_SUCCESS;
+    for (int it = 0; it < iterations && rc == SMI_SUCCESS; ++it) {
+        rc = launch_assign(points, n, dims, centroids, clusters, width, w.idx, s);
+        if (rc == SMI_SUCCESS)
+            rc = launch_accumulate(points, n, dims, w.idx, clusters, rsums(mine), rcounts(mine), w, s);
+        if (rc != SMI_SUCCESS) break;
+        if (direct) {
+            if (nr > 1) {
+                Group grp(tp);
+                rc = grp.begin(s);
+                for (int k = 0; k < nr && rc == SMI_SUCCESS; ++k) {
+                    if (k == me) continue;
+                    rc = tp->send(rsums(me), rec, k);
+                    if (rc == SMI_SUCCESS) rc = tp->recv(rsums(k), rec, k);
+                }
+                if (rc == SMI_SUCCESS) rc = grp.end();
+            }
+            if (rc == SMI_SUCCESS) rc = launch_means(rows, nr, clusters, dims, centroids, s);
+        } else {
+            rc = smi_allreduce(comm, rsums(0), rsums(1), kd, SMI_FLOAT, SMI_ADD, 0, (SMI_Stream)s);
+            if (rc == SMI_SUCCESS)
+                rc = smi_allreduce(comm, rcounts(0), rcounts(1), clusters, SMI_INT, SMI_ADD, 2, (SMI_Stream)s);
+            if (rc == SMI_SUCCESS) rc = launch_divide(rsums(1), rcounts(1), centroids, clusters, dims, s);
+        }
+    }
+    const hipError_t fe = hipFreeAsync(ws, s);
+    if (rc == SMI_SUCCESS && fe != hipSuccess) {
+        set_error(std::string("hipFreeAsync: ") + hipGetErrorString(fe));
+        rc = SMI_ERR_HIP;
+    }
+    return rc;
+}
+
 }  // namespace smi
 
 using namespace smi;
@@ -396,6 +558,32 @@ int smi_kmeans_accumulate(const float *points, int n, int dims, const int *assig
     return rc;
 }
 
+int smi_kmeans_means(const float *sums, const int *counts, int nranks, size_t ld_sums, size_t ld_counts,
+                     int clusters, int dims, float *centroids, SMI_Stream stream) {
+    SMI_ARG_CHECK(nranks >= 1 && nranks <= kMaxMeansRanks, "nranks out of range");
+    SMI_ARG_CHECK(clusters >= 1 && dims >= 1 && (long)clusters * dims < (1L << 31), "need clusters, dims >= 1");
+    SMI_ARG_CHECK(nranks == 1 || (ld_sums >= (size_t)clusters * dims && ld_counts >= (size_t)clusters),
+                  "row pitch below the row length");
+    SMI_ARG_CHECK(sums && counts && centroids, "NULL buffer");
+    MeansRows rows{};
+    for (int r = 0; r < nranks; ++r) {
+        rows.sums[r] = sums + (size_t)r * ld_sums;
+        rows.counts[r] = counts + (size_t)r * ld_counts;
+    }
+    return launch_means(rows, nranks, clusters, dims, centroids, (hipStream_t)stream);
+}
+
+int smi_kmeans_set_means(int fused) {
+    SMI_ARG_CHECK(fused <= 1, "kmeans means: 0 (reduce + bcast of sums and counts, divide) or 1 (one record exchange)");
+    if (fused >= 0) g_means_fused = fused;
+    return SMI_SUCCESS;
+}
+
+int smi_kmeans_get_means(int *fused) {
+    if (fused) *fused = g_means_fused.load();
+    return SMI_SUCCESS;
+}
+
 int smi_kmeans(SMI_Comm comm, const float *points, int n, int dims, int clusters, int width, float *centroids,
                int iterations, SMI_Stream stream) {
     Comm *c = lookup_comm(comm);
@@ -410,6 +598,8 @@ int smi_kmeans(SMI_Comm comm, const float *points, int n, int dims, int clusters
     hipStream_t s = (hipStream_t)stream;
     const size_t kd = (size_t)clusters * dims;
     const KmeansWork sz = kmeans_layout(nullptr, n, dims, clusters);
+    if (g_means_fused.load())
+        return kmeans_fused(c, comm, points, n, dims, clusters, width, centroids, iterations, sz, s);
     const size_t extra = up256(kd * 4) + up256((size_t)clusters * 4);  // reduced sums / counts
     void *ws = nullptr;
     SMI_HIP_CHECK(hipMallocAsync(&ws, sz.bytes + extra, s));

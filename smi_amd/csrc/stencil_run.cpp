@@ -1019,11 +1019,11 @@ static int solve_steps(SMI_Comm comm, float *buf0, float *buf1, const float *src
             cur ^= idx;
         }
         done = next;
-        // the same word on every rank: integer max of the patterns to rank 0
-        // and back (the float SMI_MAX starts from FLT_MIN, fold.h, and would
-        // turn a residual of 0 into 1.17549435e-38)
-        SMI_TRY(smi_reduce(comm, local, global, 1, SMI_INT, SMI_MAX, 0, 0, stream_));
-        SMI_TRY(smi_bcast(comm, global, 1, SMI_INT, 0, 0, stream_));
+        // the same word on every rank: one integer-max allreduce of the
+        // patterns (order-free, so the word smi_reduce + smi_bcast gave; the
+        // float SMI_MAX starts from FLT_MIN, fold.h, and would turn a
+        // residual of 0 into 1.17549435e-38)
+        SMI_TRY(smi_allreduce(comm, local, global, 1, SMI_INT, SMI_MAX, 0, stream_));
         SMI_HIP_CHECK(hipMemcpyAsync(c->resid_host, global, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
         SMI_HIP_CHECK(hipStreamSynchronize(s));
         r = __builtin_bit_cast(float, *c->resid_host);

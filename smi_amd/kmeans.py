@@ -70,6 +70,40 @@ def kmeans(comm: Comm, points: torch.Tensor, centroids: torch.Tensor, iterations
     return centroids
 
 
+def means(sums: torch.Tensor, counts: torch.Tensor, out: torch.Tensor | None = None,
+          stream=None) -> torch.Tensor:
+    """The cross-rank half of ComputeMeans in one kernel (smi_kmeans_means):
+    `sums` (nranks, clusters, dims) fp32 and `counts` (nranks, clusters) int32
+    hold one row per rank; returns fold(sums) / fold(counts) with the
+    rank-order folds of `reduce`.  The rank rows may be padded (any stride(0));
+    a row itself is contiguous."""
+    if sums.dtype != torch.float32 or counts.dtype != torch.int32 or not (sums.is_cuda and counts.is_cuda):
+        raise _lib.SMIError("means: sums must be a float32 and counts an int32 device tensor")
+    if sums.dim() != 3 or counts.dim() != 2 or counts.shape != sums.shape[:2]:
+        raise _lib.SMIError("means: sums is (nranks, clusters, dims), counts (nranks, clusters)")
+    nranks, clusters, dims = sums.shape
+    if (dims > 1 and sums.stride(2) != 1) or (clusters > 1 and (sums.stride(1) != dims or counts.stride(1) != 1)):
+        raise _lib.SMIError("means: the row of a rank must be contiguous")
+    if out is None:
+        out = torch.empty((clusters, dims), dtype=torch.float32, device=sums.device)
+    _check(out, torch.float32, "out")
+    _lib.call("smi_kmeans_means", sums.data_ptr(), counts.data_ptr(), nranks, sums.stride(0), counts.stride(0),
+              clusters, dims, out.data_ptr(), _lib.stream_handle(stream))
+    return out
+
+
+def set_means(fused: int) -> int:
+    """How `kmeans` combines the ranks' sums and counts: 0 = reduce + bcast of
+    each and a divide (default), 1 = one record exchange and one `means`
+    launch per iteration; -1 keeps the setting.  Process-wide, the same on
+    every rank.  Returns the setting now in force."""
+    import ctypes
+    _lib.call("smi_kmeans_set_means", fused)
+    v = ctypes.c_int()
+    _lib.call("smi_kmeans_get_means", ctypes.byref(v))
+    return v.value
+
+
 def split_points(points: np.ndarray, size: int, rank: int) -> np.ndarray:
     """MPI_Scatter of kmeans_smi.cpp:165-166: equal contiguous shares."""
     if len(points) % size:
